@@ -16,11 +16,17 @@ Default workload (N=1): the configuration BASELINE.json's metric is quoted on â€
 (32 MoE layers x 8 experts, H=4096 F=14336, top-2, bf16; 84 GiB of experts), device_memory_ratio
 0.75, batch 1, synthetic weights N(0, 0.02^2) and RMS-normalised activations.
 
-The timed region is W warm-up steps, then EXACTLY K steps between barrier + synchronize; that K-step window
-is repeated (default 5 windows in total) and `value` is the MEDIAN window (`windows_ms` lists all of them, the
-first one is the contract's window).
+The timed region is W warm-up steps, then EXACTLY K steps between barrier + synchronize.  A plain run times that K-step
+window once and does nothing else: set-up, warm-up, the K steps, the outputs (--dump-outputs DIR), the line.  With
+--full the window is repeated (default 5 windows in total) and `value` is the MEDIAN window (`windows_ms` lists all of
+them, the first one is the contract's window).
 
-Further legs of the same line (N=1 only; none of them touches `value`):
+--dump-outputs DIR: what the timed path returned in its last timed step, every MoE layer's output [L, B, H] as float32,
+into DIR/moe_out.npy (DIR/moe_out_rank<r>.npy per rank when N > 1).  Inputs and weights are seeded: the same arguments
+give the same inputs in every run, so two builds can be compared output for output.
+
+Further legs of the same line, run only with --full (N=1 only; none of them touches `value`):
+  prefill        the --prompt tokens through every layer, timed apart from the decode steps
   roofline       the K steps again with HIP events around every kernel of the path, on the launch stream
   parity         sampled (step, layer) pairs at FULL size against the oracle with the tests' own bars
                  (oracle/parity.py), ASSERTED: a parity miss makes the process exit non-zero after the line
@@ -29,8 +35,10 @@ Further legs of the same line (N=1 only; none of them touches `value`):
                  (moeinf_set_cache_budget): hit rate, H2D GB/s, exposed wait, overlap, PCIe-bound estimate
   other_configs  BASELINE configs 2, 5 and 1 in short form: DeepSeek-V2-Lite batch 1, NLLB-MoE-54B batch 32,
                  Switch-base-8 batch 1 (fp32)
-With N > 1 (or --force-ep) the line carries parity (every rank checks its own tokens through the exchange path),
-cpu_baseline (rank 0) and ep_phases_us_per_layer.
+  dropin         the drop-in path (prefetch_op.expert_dispatcher) timed beside the fused path
+  traffic        roofline.traffic measured live by two rocprofv3 --pmc child runs
+With N > 1 (or --force-ep) and --full the line carries parity (every rank checks its own tokens through the exchange path),
+cpu_baseline (rank 0), ep_phases_us_per_layer and the step time over every transport that works.
 """
 import argparse
 import json
@@ -174,7 +182,7 @@ def measure_traffic_live(workload, kernel_substr, timeout_s=170):
     if not rp:
         return None, "rocprofv3 not found"
     vals = {}
-    cmd_tail = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
+    cmd_tail = [sys.executable, os.path.abspath(__file__), "--full", "--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
                 "--miss-heavy-frac", "0", "--windows", "1", "--layers", "8", "--prompt", "0", "--no-traffic"]
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="moeinf_pmc_", dir="/tmp")
@@ -241,6 +249,8 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     nsteps = warmup + steps
     xs = [[acts(B, H, dt, 2024 + l + 1000 * s + 100000 * rank).to(dev) for l in range(L)] for s in range(nsteps)]
     out = torch.empty(B, H, dtype=dt, device=dev)
+    # the last step of a timed window writes every layer into its own buffer: what a caller of the path receives (--dump-outputs)
+    outs = torch.empty(L, B, H, dtype=dt, device=dev)
     batch_rows = B if family == "switch" else 1
 
     ep = None
@@ -309,16 +319,17 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
             ep.drop_native()  # collective: every rank gives the candidate's windows / buffers back
         log("expert-parallel transport: " + ep.transport + " | " + " | ".join(ep_notes))
 
-        def layer_fwd(l, x):
-            ep.forward(l, x, gates[l], out=out)
+        def layer_fwd(l, x, o=out):
+            ep.forward(l, x, gates[l], out=o)
     else:
-        def layer_fwd(l, x):
-            eng.forward(l, x, gates[l], batch_rows=batch_rows, out=out)
+        def layer_fwd(l, x, o=out):
+            eng.forward(l, x, gates[l], batch_rows=batch_rows, out=o)
 
-    def run_steps(s0, n):
+    def run_steps(s0, n, keep_last=False):
         for s in range(s0, s0 + n):
+            last = keep_last and s == s0 + n - 1
             for l in range(L):
-                layer_fwd(l, xs[s][l])
+                layer_fwd(l, xs[s][l], outs[l] if last else out)
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -337,9 +348,9 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     warm = eng.stats()
     log(f"{label}: cache warm ({warm['slots_used']} experts resident) in {time.time() - t0:.1f}s, h2d {warm['h2d_bytes'] / 2**30:.1f} GiB, link-busy {warm['h2d_busy_ms']:.0f} ms")
     # prefill of the prompt (B sequences x --prompt tokens) through every layer: exercises the large-T
-    # path; timed separately, NOT part of `value`
+    # path; timed separately, NOT part of `value` (--full; the engine is sized for the prompt either way)
     prefill_ms, prefill_passes, prefill_kernels = None, None, None
-    if prompt > 0 and not use_ep:
+    if prompt > 0 and not use_ep and args.full:
         xp = acts(B * prompt, H, dt, 777).to(dev)
         outp = torch.empty_like(xp)
         for l in range(L):  # untimed pass: makes every expert the prompt touches resident
@@ -395,7 +406,7 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     for w in range(max(1, args.windows)):
         fence()
         t0 = time.perf_counter()
-        run_steps(warmup, steps)
+        run_steps(warmup, steps, keep_last=True)
         fence()
         elapsed = time.perf_counter() - t0
         if world > 1:
@@ -407,11 +418,13 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     ms_per_step = elapsed * 1e3 / steps
     tokens_per_s = world * B * steps / elapsed
     st = eng.stats()
+    if main and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, rank if world > 1 else None, DUMP_MAX_BYTES // world)
 
     # ---- expert-parallel runs: the same K steps once more with per-phase timers (pack / all-to-all / owner FFN /
     # all-to-all / combine), so a scaling run is diagnosable from its one line
     ep_phases = None
-    if ep is not None:
+    if ep is not None and args.full:
         try:
             ep.profile = True
             fence()
@@ -426,7 +439,7 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     # all-to-all; the default prefers the direct peer-store exchange): one window each, same barrier / max-over-ranks bracket.
     # Every rank runs the same sequence of collectives: the constructors' verdicts are all-reduced inside ExpertParallelMoE.
     by_transport = None
-    if ep is not None and world > 1:
+    if ep is not None and world > 1 and args.full:
         by_transport = {ep.transport: round(ms_per_step, 4)}
         chosen_ep, chosen_name = ep, ep.transport
 
@@ -467,17 +480,18 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     # owner-side FFN launches of THIS rank, and rank 0 reports its own kernels.
     roof, kernels = None, {}
     p = None
-    try:
-        eng.set_profiling(True)
-        fence()
-        run_steps(warmup, steps)
-        fence()
-        p = eng.profile()
-        eng.set_profiling(False)
-    except Exception as ex:  # the measured line above must survive a failure of this extra leg in multi-rank runs
-        if world == 1:
-            raise
-        log(f"roofline leg failed on rank {rank}: {ex!r}")
+    if args.full:
+        try:
+            eng.set_profiling(True)
+            fence()
+            run_steps(warmup, steps)
+            fence()
+            p = eng.profile()
+            eng.set_profiling(False)
+        except Exception as ex:  # the measured line above must survive a failure of this extra leg in multi-rank runs
+            if world == 1:
+                raise
+            log(f"roofline leg failed on rank {rank}: {ex!r}")
     if p is not None:
 
         def kstat(ms, launches, nbytes):
@@ -564,7 +578,7 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     # owned by other ranks are regenerated from their seeds for the oracle); rank 0 times the oracle first, alone.
     cpu = None
     parity = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import moe_ref as R
         from oracle import parity as P
 
@@ -731,6 +745,8 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
     from bench_legs import offload as _offload
 
     offload_frac = args.miss_heavy_frac if (main or force_offload) else (args.offload_frac_other if family == "deepseek" else 0.0)
+    if not args.full:
+        offload_frac = 0.0
 
     miss = _offload.offload_regime(types.SimpleNamespace(**{k: v for k, v in locals().items() if k in _offload.NEEDS}))
     res = {"label": label, "family": family, "cfg": cfg, "L": L, "E": E, "K": K, "H": H, "B": B, "dt": dt,
@@ -745,6 +761,28 @@ def run_workload(args, workload, B, world, rank, local_rank, dev, use_ep, main, 
                "candidates": ep_notes}}
     eng.close()
     return res
+
+
+DUMP_MAX_BYTES = 64 * 2**20
+
+
+def dump_outputs(d, outs, rank=None, limit=DUMP_MAX_BYTES):
+    """outs [L, B, H] (the last timed step's per-layer outputs) -> d/moe_out.npy in float32.  Past `limit` bytes (this rank's
+    share of DUMP_MAX_BYTES) a fixed, seeded sample of the L*B rows is written instead, with the sampled row numbers in
+    moe_out_rows.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank is None else f"_rank{rank}"
+    a = outs.float().cpu().numpy()
+    if a.nbytes > limit:
+        rows = a.reshape(-1, a.shape[-1])
+        keep = max(1, limit // (2 * rows.shape[1] * 4))
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+        a = rows[idx]
+        np.save(os.path.join(d, f"moe_out_rows{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, f"moe_out{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {d} ({a.nbytes} B, shape {list(a.shape)})")
 
 
 def comm_dev(dist, dev):
@@ -779,7 +817,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5, help="how many times the K-step window is timed (median reported)")
+    ap.add_argument("--windows", type=int, default=None, help="how many times the K-step window is timed (median reported; default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline: prefill, roofline, CPU baseline + parity, offload regime, other configs, drop-in, live traffic, "
+                         "per-transport and per-phase timing of expert-parallel runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-layer outputs of the last timed step to DIR/moe_out.npy (float32, [L, B, H])")
     ap.add_argument("--workload", default="mixtral-8x7b", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=1, help="decode batch (new tokens per step) per rank")
     ap.add_argument("--ratio", type=float, default=0.75, help="device_memory_ratio")
@@ -806,6 +849,8 @@ def main():
     ap.add_argument("--dropin-layers", type=int, default=4, help="full-size MoE layers of the drop-in leg (its offload directory holds every expert of them: 8 Mixtral layers = 21 GiB)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the live HBM-traffic pass (two rocprofv3 --pmc child runs, ~1 min): roofline.traffic then comes from profiles/ (static)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -849,7 +894,7 @@ def main():
         main_dtype = Cf_.DTYPE_F16 if args.dtype == "fp16" else Cf_.DTYPE_F8E4M3
     r = run_workload(args, args.workload, args.batch, world, rank, local_rank, dev, use_ep, True, dist, dtype_id=main_dtype)
     # roofline.traffic measured in THIS run (the main engine is closed: its HBM and pinned memory are free for the children)
-    if rank == 0 and world == 1 and not use_ep and not args.no_traffic and r.get("roof"):
+    if rank == 0 and world == 1 and not use_ep and args.full and not args.no_traffic and r.get("roof"):
         t0 = time.time()
         sub = "ffn1_selfroute_kernel" if r.get("selfroute") else "ffn_rows_kernel"
         tb, note = measure_traffic_live(args.workload, sub)
@@ -865,7 +910,8 @@ def main():
         else:
             r["roof"]["traffic_live_attempt"] = note
     others = []
-    default_main = (args.workload == "mixtral-8x7b" and args.batch == 1 and not args.layers and not args.budget_gib and args.dtype == "model")
+    default_main = (args.full and args.workload == "mixtral-8x7b" and args.batch == 1 and not args.layers and not args.budget_gib
+                    and args.dtype == "model")
     if world == 1 and not use_ep and default_main and not args.no_other_configs:
         for wl, b in (("deepseek-v2-lite", 1), ("nllb-moe-54b", 32), ("switch-base-8", 1)):
             try:

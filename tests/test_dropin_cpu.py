@@ -1,62 +1,32 @@
 """The drop-in boundary on CPU: our mirror of ``DistributedExpertExecutor.dispatch_local`` (12 lines restated from
 moe_infinity/distributed/expert_executor.py:32-58 — an interface mirror, not a design of ours) must drive a dispatcher
-exactly like the reference's own function does.  Runs the REFERENCE'S code from /root/reference when it is there
-(build container); the GPU tests then use the mirror with the real dispatcher."""
+exactly like the reference's own function does.  What the reference's function called is recorded in
+tests/golden/reference_call_traces.json (oracle/gen_golden_calls.py ran it); the GPU tests then use the mirror with the
+real dispatcher."""
+import json
 import os
 
 import pytest
 import torch
 
-REF = "/root/reference"
+from oracle.gen_golden_calls import run_dispatch_case
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_call_traces.json")
 
 
-class Recorder:
-    """expert_dispatcher stand-in that records the call sequence"""
-
-    def __init__(self):
-        self.calls = []
-
-    def set_inputs(self, hidden, mask):
-        self.calls.append(("set_inputs", tuple(hidden.shape), tuple(mask.shape), int(mask.sum())))
-
-    def set_expected_queue(self, n):
-        self.calls.append(("set_expected_queue", int(n)))
-
-    def enqueue_expert(self, layer, expert, gpu, remote):
-        self.calls.append(("enqueue_expert", int(layer), int(expert), int(gpu), bool(remote)))
-
-    def wait_expert(self):
-        self.calls.append(("wait_expert",))
-        return [("result", len(self.calls))]
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs /root/reference")
 def test_dispatch_local_mirror_drives_the_dispatcher_like_the_reference_does(monkeypatch):
     from moe_infinity_amd.expert_executor import DistributedExpertExecutor as Ours
-    from oracle.gen_golden import import_reference
 
-    mods = import_reference()
-    Theirs = mods["executor"].DistributedExpertExecutor
-    monkeypatch.setattr(torch.cuda, "device_count", lambda: 3)  # gpu_id = expert_id % device_count
-    g = torch.Generator().manual_seed(3)
-    for trial in range(25):
-        t, e = int(torch.randint(1, 40, (1,), generator=g)), int(torch.randint(2, 130, (1,), generator=g))
-        mask = torch.rand(t, e, generator=g) < (2.0 / e)
-        if trial % 5 == 0:
-            mask[:] = False  # nothing routed: empty expert list
-        hidden = torch.randn(t, 16, generator=g)
-        a, b = Recorder(), Recorder()
-        ra, rb = Theirs(None), Ours(None)
-        ra.set_expert_dispatcher(a)
-        rb.set_expert_dispatcher(b)
-        layer = trial % 7
-        out_a = ra.dispatch_local(hidden, mask, layer)
-        out_b = rb.dispatch_local(hidden, mask, layer)
-        assert a.calls == b.calls and out_a == out_b
-        # 3-D masks ([B, S, E]) are viewed (-1, E) by both
-        out_a = ra.dispatch_local(hidden[None], mask[None], layer)
-        out_b = rb.dispatch_local(hidden[None], mask[None], layer)
-        assert a.calls == b.calls and out_a == out_b
+    gold = json.load(open(GOLD))["dispatch_local"]
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: gold["device_count"])  # gpu_id = expert_id % device_count
+    cases = gold["cases"]
+    assert len(cases) == 25 and any(not c["mask"] for c in cases) and max(c["e"] for c in cases) > 64
+    for case in cases:
+        got = run_dispatch_case(Ours, case)
+        # [T, E] masks, then the same mask as [B, S, E] (viewed (-1, E) by both), on one dispatcher
+        for form in ("2d", "3d"):
+            assert got[form]["calls"] == case[form]["calls"], (case["layer"], case["t"], case["e"], form)
+            assert got[form]["out"] == case[form]["out"]
 
 
 def test_prefetch_op_exports_the_pybind_surface():

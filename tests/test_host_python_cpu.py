@@ -134,49 +134,29 @@ def test_prefetch_handle_adapter_keeps_the_reference_method_names_and_order():
 
 
 def test_reference_expert_prefetcher_drives_the_adapter_unmodified():
-    """The reference's own memory/expert_prefetcher.py (imported from /root/reference when it is there; CPU-only
-    build container) against the adapter: same protected set and the same prefetch order as our mirror class."""
-    import importlib.util
+    """The reference's own memory/expert_prefetcher.py against the adapter: every call it made on a PrefetchHandle, with its
+    arguments and what the adapter returned, is recorded in tests/golden/reference_call_traces.json (oracle/gen_golden_calls.py
+    ran the reference's file).  Replayed on the adapter over the recording engine, the calls must get the same answers and give
+    the same protected set and the same prefetch order as our mirror class."""
     import os
-    import sys
-    import types
 
-    src = "/root/reference/moe_infinity/memory/expert_prefetcher.py"
-    if not os.path.exists(src):
-        pytest.skip("reference checkout not present")
     from moe_infinity_amd.memory import ExpertPrefetcher, ExpertTracer
     from moe_infinity_amd.prefetch_handle import PrefetchHandle
 
-    # the module imports moe_infinity.utils.parse_moe_param; stub the package around the one file we want
-    L, E = 3, 4
-    stub = types.ModuleType("moe_infinity")
-    utils = types.ModuleType("moe_infinity.utils")
-    utils.parse_moe_param = lambda config: (L, E, 0)
-    stub.utils = utils
-    saved = {k: sys.modules.get(k) for k in ("moe_infinity", "moe_infinity.utils")}
-    sys.modules["moe_infinity"], sys.modules["moe_infinity.utils"] = stub, utils
-    sys.dont_write_bytecode = True
-    try:
-        spec = importlib.util.spec_from_file_location("ref_expert_prefetcher", src)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_call_traces.json")) as f:
+        gold = json.load(f)["expert_prefetcher"]
+    L, E = gold["L"], gold["E"]
     tmap = {(l, e): 100 + 10 * l + e for l in range(L) for e in range(E)}
-    m = np.array([[0, 0, 0, 0], [0.5, 0, 0.25, 0], [0, 0.125, 0, 0.75]])
+    m = np.array(gold["matrix"])
     ref_eng = _RecordingEngine()
-    ref = mod.ExpertPrefetcher(config=None)
-    ref.set_archer_engine(PrefetchHandle(ref_eng, tmap))
-    ref.expert_tensor_map = tmap
-    ref.prefetch_experts(1, m)
+    handle = PrefetchHandle(ref_eng, tmap)
+    assert [c[0] for c in gold["adapter_calls"]][:1] == ["replace_cache_candidates"] and len(gold["adapter_calls"]) > 1
+    for name, args, ret in gold["adapter_calls"]:
+        assert getattr(handle, name)(*args) == ret, (name, args)
     ours_eng = _RecordingEngine()
     ours = ExpertPrefetcher(L, E, ExpertTracer(4, L, E))
     ours.set_archer_engine(ours_eng)
-    ours.prefetch_experts(1, m)
+    ours.prefetch_experts(gold["layer"], m)
 
     def flat(calls):
         prot = [c[1] for c in calls if c[0] == "protect"]

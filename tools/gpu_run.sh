@@ -8,7 +8,7 @@
 #   build                 __graft_entry__.build()
 #   pytest[:<expr>]       python -m pytest tests -m gpu [-k <expr>]
 #   smoke                 __graft_entry__.smoke()
-#   bench                 the driver's command: python bench.py --gpus 1 --steps 20 --warmup 5
+#   bench                 the driver's command with every leg: python bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   bench2                two ranks on this one GPU over the peer-store transport (8 layers)
 #   kt:<workload>[:B]     rocprofv3 --kernel-trace --stats of a lean bench of <workload> (decode batch B)
 #   pmc:<workload>:<C>[:B] rocprofv3 --pmc <C> --kernel-trace (C = one counter set, '+'-separated) over 8 layers
@@ -20,7 +20,7 @@ export TMPDIR=/tmp
 R=$(pwd)
 TAG=${1:?tag}; shift
 OUT=gpurun_out/$TAG; mkdir -p "$OUT"
-LEAN="--no-cpu-baseline --no-other-configs --miss-heavy-frac 0 --windows 1 --no-traffic"
+LEAN="--full --no-cpu-baseline --no-other-configs --miss-heavy-frac 0 --windows 1 --no-traffic"
 for task in "$@"; do
   IFS=':' read -r kind a1 a2 a3 a4 <<< "$task"
   case "$kind" in
@@ -34,12 +34,12 @@ for task in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log" ;;
     bench)
-      ( time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2> "$OUT/bench_default.time"
+      ( time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2> "$OUT/bench_default.time"
       echo "bench exit $? line bytes $(wc -c < "$OUT/bench_default.json")"; tail -3 "$OUT/bench_default.time"
       cp bench_details.json "$OUT/bench_default_details.json" 2>/dev/null
       grep -E "live traffic|failed|FAILED" "$OUT/bench_default.err" | tail -6 ;;
     bench2)
-      MOEINF_BENCH_SHARE_GPU0=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --no-other-configs \
+      MOEINF_BENCH_SHARE_GPU0=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 2 --full --no-other-configs \
         --layers 8 --cpu-sample-layers 4 --cpu-sample-steps 2 > "$OUT/bench_two_ranks_one_gpu.json" 2> "$OUT/bench_two_ranks_one_gpu.err"
       echo "two-rank bench exit $?"; cp bench_details.json "$OUT/bench_two_ranks_details.json" 2>/dev/null ;;
     kt)

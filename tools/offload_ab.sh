@@ -8,7 +8,7 @@ for rnd in 0 1; do
 for setting in ${@:-base}; do
   tag=${setting//[=,]/_}
   envs=(); [ "$setting" != base ] && IFS=',' read -r -a envs <<< "$setting"
-  env "${envs[@]}" timeout 900 python bench.py --workload $WL --no-cpu-baseline --no-other-configs --no-traffic --no-dropin \
+  env "${envs[@]}" timeout 900 python bench.py --full --workload $WL --no-cpu-baseline --no-other-configs --no-traffic --no-dropin \
     --miss-heavy-frac 0.5 --prompt 0 --windows 1 --steps 6 --warmup 2 ${OFFLOAD_AB_FLAGS:-} > "$OUT/offload_${tag}_$rnd.json" 2> "$OUT/offload_${tag}_$rnd.err"
   cp bench_details.json "$OUT/offload_${tag}_${rnd}_details.json"
   python - "$OUT/offload_${tag}_${rnd}_details.json" "$setting" <<'PY'
