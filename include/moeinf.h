@@ -41,7 +41,8 @@ enum {
 enum { MOEINF_DTYPE_BF16 = 0, MOEINF_DTYPE_F32 = 1, MOEINF_DTYPE_F16 = 2,
        /* the reference's id 3 (core/parallel/expert_module.h:23,118-119 -> torch::kFloat8_e4m3fn): expert blobs are e4m3fn bytes in
         * the HOST tier and on the link (half of bf16's: half the copy time of every miss), up-cast to bf16 when pulled into their HBM
-        * slot; activations, gate and arithmetic are bf16 — y = FFN(x; W.to(bf16)) (round 6) */
+        * slot; activations, gate and arithmetic are bf16 — y = FFN(x; W.to(bf16)) (round 6).  With fp8 slots (moeinf_create_ex,
+        * slot_dtype = MOEINF_DTYPE_F8E4M3) they stay fp8 in the slot too and the FFN kernels up-cast in registers: same y */
        MOEINF_DTYPE_F8E4M3 = 3 };
 
 /* expert_type ids: core/parallel/expert_module.h:13-18, moe_infinity/common/constants.py:29-37 */
@@ -160,6 +161,24 @@ int moeinf_fence_cover_pos(const uint64_t* fence_seq, uint64_t recorded, uint64_
  * (core/prefetch/archer_prefetch_handle.cpp:18-64,73-81) */
 int moeinf_create(const moeinf_config* cfg, moeinf_engine** out);
 int moeinf_destroy(moeinf_engine* eng);
+
+/* Creation options that do not fit the ABI-4 structs.  struct_bytes = sizeof(moeinf_create_options); reserved must be zero.
+ * slot_dtype: the dtype the HBM expert slots hold.  A NULL options pointer, cfg->dtype (fp8 experts: MOEINF_DTYPE_BF16): what
+ * moeinf_create does.
+ * MOEINF_DTYPE_F8E4M3 ("fp8 slots"): fp8 experts (cfg->dtype == MOEINF_DTYPE_F8E4M3) stay fp8 in their slots — half the slot
+ * bytes, so about twice the experts per device budget — and the decode FFN kernels stream fp8 weights and up-cast them in
+ * registers; activations, gate, shared expert, epilogues and accumulation stay bf16/fp32, so y = FFN(x; W.to(bf16)) as with
+ * bf16 slots.  Accepted for Mixtral / DeepSeek experts (routers: Mixtral, softmax-top-k, DeepSeek, DeepSeek-V3), ep_size == 1,
+ * hidden % 64 == 0 and inter % 64 == 0; anything else is MOEINF_ERR_UNSUPPORTED with the reason.  Stages with many rows per
+ * expert (prefill) run the row kernel's four-token-tile form: the grouped GEMMs are not built for fp8 weights. */
+typedef struct moeinf_create_options {
+  int32_t struct_bytes;
+  int32_t slot_dtype;
+  int32_t reserved[6];
+} moeinf_create_options;
+int moeinf_create_ex(const moeinf_config* cfg, const moeinf_create_options* opts, moeinf_engine** out);
+/* the dtype the engine's HBM expert slots hold (MOEINF_DTYPE_*) */
+int moeinf_slot_dtype(const moeinf_engine* eng, int32_t* slot_dtype);
 
 /* ---- expert blobs --------------------------------------------------------------------------
  * The reference keeps one contiguous, 4 KiB-aligned blob per expert with the tensors in

@@ -68,6 +68,10 @@ class EpProfile(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CreateOptions(C.Structure):  # moeinf_create_options (creation options outside the ABI-4 config struct)
+    _fields_ = [("struct_bytes", C.c_int32), ("slot_dtype", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _I64P = C.POINTER(C.c_int64)
@@ -84,6 +88,8 @@ PROTOTYPES = {
     "moeinf_fence_ring": (C.c_int, []),
     "moeinf_fence_cover_pos": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64]),
     "moeinf_create": (C.c_int, [C.POINTER(Config), C.POINTER(_P)]),
+    "moeinf_create_ex": (C.c_int, [C.POINTER(Config), C.POINTER(CreateOptions), C.POINTER(_P)]),
+    "moeinf_slot_dtype": (C.c_int, [_P, _I32P]),
     "moeinf_destroy": (C.c_int, [_P]),
     "moeinf_expert_layout": (C.c_int, [_P, C.c_int, _I64P, _I64P, _I32P, _I64P]),
     "moeinf_register_expert": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),

@@ -11,7 +11,10 @@ from typing import Optional
 
 # ids shared with include/moeinf.h (and core/parallel/expert_module.h in the reference)
 DTYPE_BF16, DTYPE_F32, DTYPE_F16 = 0, 1, 2
-DTYPE_F8E4M3 = 3  # fp8 (e4m3fn) experts in the host tier, up-cast to bf16 in their HBM slot; activations / gate / arithmetic bf16
+# fp8 (e4m3fn) experts in the host tier; activations / gate / arithmetic bf16, y = FFN(x; W.to(bf16)) in both modes.  Default: up-cast
+# to bf16 as they are pulled into their HBM slot.  EngineConfig.fp8_slots: they stay fp8 in the slot (half the bytes: about twice the
+# experts per device budget) and the FFN kernels up-cast in registers
+DTYPE_F8E4M3 = 3
 EXPERT_SWITCH, EXPERT_SWITCH_GATED, EXPERT_NLLB, EXPERT_FSGPT, EXPERT_MIXTRAL, EXPERT_DEEPSEEK = 0, 1, 2, 3, 4, 5
 ROUTER_MIXTRAL, ROUTER_DEEPSEEK, ROUTER_SWITCH, ROUTER_NLLB, ROUTER_SOFTMAX_TOPK, ROUTER_DEEPSEEK_V3 = 0, 1, 2, 3, 4, 5
 POLICY_LFU_INCACHE, POLICY_LRU = 0, 1
@@ -77,6 +80,9 @@ class EngineConfig:
     ep_rank: int = 0
     ep_size: int = 1
     max_tokens: int = 64
+    # fp8 experts (dtype DTYPE_F8E4M3) keep fp8 in their HBM slots (moeinf_create_ex): Mixtral / DeepSeek experts, ep_size 1,
+    # hidden and inter multiples of 64.  Not part of the C config struct.
+    fp8_slots: bool = False
 
     def to_dict(self):
         return asdict(self)

@@ -234,7 +234,45 @@ extern "C" int moeinf_destroy(moeinf_engine* g) {
 }
 
 static void prealloc_slots(moeinf_engine* g);
-extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) {
+static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine** out);
+extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, false, out); }
+
+// fp8 slots: what the fp8-weight kernels cover (kernels.hip / layer_fused.hip: the row-dot forms of the gated families); every
+// other configuration is refused here, so the kernels that have no fp8 form (grouped GEMMs are declined by their launchers; the
+// Switch one-launch layer, the expert-parallel owner kernels) are never reached
+static int check_fp8_slots(const moeinf_config* c) {
+  if (c->dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need fp8 experts (dtype %d, not %d)", MOEINF_DTYPE_F8E4M3, c->dtype);
+  if (c->expert_type != MOEINF_EXPERT_MIXTRAL && c->expert_type != MOEINF_EXPERT_DEEPSEEK)
+    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots are built for Mixtral and DeepSeek experts only (expert_type %d)", c->expert_type);
+  if (c->router_kind != MOEINF_ROUTER_MIXTRAL && c->router_kind != MOEINF_ROUTER_SOFTMAX_TOPK && c->router_kind != MOEINF_ROUTER_DEEPSEEK &&
+      c->router_kind != MOEINF_ROUTER_DEEPSEEK_V3)
+    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots: router_kind %d is not one of the Mixtral / DeepSeek families'", c->router_kind);
+  if (c->ep_size != 1) return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots are not built for expert parallelism (ep_size %d)", c->ep_size);
+  if (c->hidden <= 0 || c->inter <= 0 || c->hidden % 64 || c->inter % 64)
+    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need hidden and inter to be multiples of 64 (one fp8 tile: 64 k), not %d / %d", c->hidden, c->inter);
+  return MOEINF_OK;
+}
+extern "C" int moeinf_create_ex(const moeinf_config* cfg, const moeinf_create_options* opts, moeinf_engine** out) {
+  if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!cfg) return fail(MOEINF_ERR_INVALID, "cfg is NULL");
+  if (!opts) return create_engine(cfg, false, out);
+  if (opts->struct_bytes != (int32_t)sizeof(moeinf_create_options)) return fail(MOEINF_ERR_INVALID, "options.struct_bytes %d != %d", opts->struct_bytes, (int)sizeof(moeinf_create_options));
+  for (int i = 0; i < 6; ++i) if (opts->reserved[i]) return fail(MOEINF_ERR_INVALID, "options.reserved[%d] must be zero", i);
+  // (fp8 experts: slot_dtype bf16 = today's engine, the pull kernel up-casts into bf16 slots)
+  const bool plain = opts->slot_dtype == cfg->dtype || (cfg->dtype == MOEINF_DTYPE_F8E4M3 && opts->slot_dtype == MOEINF_DTYPE_BF16);
+  if (plain && opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return create_engine(cfg, false, out);
+  if (opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "slot_dtype %d with dtype %d: only fp8 slots (%d) for fp8 experts are built", opts->slot_dtype, cfg->dtype, MOEINF_DTYPE_F8E4M3);
+  CHK(check_fp8_slots(cfg));
+  return create_engine(cfg, true, out);
+}
+extern "C" int moeinf_slot_dtype(const moeinf_engine* g, int32_t* slot_dtype) {
+  if (!g || !slot_dtype) return fail(MOEINF_ERR_INVALID, "engine or slot_dtype is NULL");
+  *slot_dtype = g->slot_f8 ? MOEINF_DTYPE_F8E4M3 : g->cfg.dtype;
+  return MOEINF_OK;
+}
+
+static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine** out) {
   if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
   *out = nullptr;
   // fp8 experts (the reference's dtype id 3, core/parallel/expert_module.h:23,118-119): e4m3fn bytes in the HOST tier and on the link,
@@ -273,7 +311,10 @@ extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) {
   g->host_es = host_f8 ? 1 : g->es;
   g->lay = make_layout(cfg->expert_type, g->H, g->F, g->host_es);
   if (g->has_shared) g->lay_sh = make_layout(cfg->expert_type, g->H, g->Fs, g->host_es);
-  g->dlay = make_dev_layout(cfg->expert_type, g->H, g->F, g->dt, g->es);
+  // fp8 slots: the routed experts' tiles hold e4m3fn bytes (pull_retile_kernel<uint8_t, false>); the shared expert stays bf16
+  g->slot_f8 = slot_f8 && host_f8;
+  g->slot_dt = g->slot_f8 ? DT_F8 : g->dt;
+  g->dlay = make_dev_layout(cfg->expert_type, g->H, g->F, g->slot_dt, g->slot_f8 ? 1 : g->es);
   if (g->has_shared) g->dlay_sh = make_dev_layout(cfg->expert_type, g->H, g->Fs, g->dt, g->es);
   g->slot_bytes = g->dlay.total;
   g->nodes.resize((size_t)g->L * g->E);
@@ -659,14 +700,14 @@ static int issue_copy(moeinf_engine* g, int idx, CopyLane& ln, bool allow_protec
     auto pull = [&](int k0, int k1) -> int {
       RetileBlob rb;
       memset(&rb, 0, sizeof rb);
-      rb.src = n.host; rb.dst = s.dev; rb.n = 0; rb.src_f8 = g->host_f8 ? 1 : 0;
+      rb.src = n.host; rb.dst = s.dev; rb.n = 0; rb.src_f8 = (g->host_f8 && !g->slot_f8) ? 1 : 0;  // (fp8 slots: bytes as they are)
       for (int k = k0; k < k1; ++k) {
         const int i = order[k], j = rb.n++;
         rb.src_off[j] = g->lay.off[i]; rb.dst_off[j] = g->dlay.off[i];
         rb.K[j] = g->dlay.K[i];
         rb.R[j] = g->dlay.K[i] > 0 ? g->dlay.R[i] : (int)(g->dlay.size[i] / 16);
       }
-      HIPCHK(launch_pull_retile(rb, g->dt, g->h2d_pull_wgs, ln.copy, ts, launches == 0 ? 1 : 0));
+      HIPCHK(launch_pull_retile(rb, g->slot_dt, g->h2d_pull_wgs, ln.copy, ts, launches == 0 ? 1 : 0));
       launches += 1;
       return MOEINF_OK;
     };
@@ -998,6 +1039,7 @@ void fill_stage(const moeinf_engine* g, int layer, int stage, FfnStage& s, int64
   s.n_active_host = -1;
   s.E = g->E;
   s.dtype = g->dt;
+  s.wdtype = g->slot_dt;  // (the routed experts' weights; the shared expert's are always `dtype`)
   s.rows_bound = (int64_t)g->cfg.max_tokens * (g->K + 1);
   const int et = g->cfg.expert_type;
   if (stage == 1) {
@@ -1037,8 +1079,9 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   const int et = g->cfg.expert_type;
   const bool gated = (et == MOEINF_EXPERT_MIXTRAL || et == MOEINF_EXPERT_DEEPSEEK || et == MOEINF_EXPERT_SWITCH_GATED);
   const bool bias = (et == MOEINF_EXPERT_NLLB || et == MOEINF_EXPERT_FSGPT);
-  const int64_t b1 = U * ((gated ? 2 : 1) * F * H * es + (bias ? F * es : 0)) + (Tsh ? 2 * Fs * H * es : 0) + (rows + Tsh) * H * es + rows * F * es + Tsh * Fs * es;
-  const int64_t b2 = U * (H * F * es + (bias ? H * es : 0)) + (Tsh ? H * Fs * es : 0) + rows * F * es + Tsh * Fs * es + (rows + Tsh) * H * es;
+  const int64_t wes = g->slot_f8 ? 1 : es;  // routed weight bytes per element (fp8 slots: 1)
+  const int64_t b1 = U * ((gated ? 2 : 1) * F * H * wes + (bias ? F * es : 0)) + (Tsh ? 2 * Fs * H * es : 0) + (rows + Tsh) * H * es + rows * F * es + Tsh * Fs * es;
+  const int64_t b2 = U * (H * F * wes + (bias ? H * es : 0)) + (Tsh ? H * Fs * es : 0) + rows * F * es + Tsh * Fs * es + (rows + Tsh) * H * es;
   g->prof.ffn1_bytes += b1;
   g->prof.ffn2_bytes += b2;
   if (local) {
@@ -1532,6 +1575,7 @@ void hidden_shared_stages(const moeinf_engine* g, int layer, const void* x_dev, 
   sh1.in = x_dev; sh1.row_map = nullptr; sh1.out = g->d_h_sh; sh1.ld_out = g->Fs;
   fill_stage(g, layer, 2, sh2, 0);
   sh2.in = g->d_h_sh; sh2.ld_in = g->Fs; sh2.out = g->d_y_sh; sh2.out_map = nullptr;
+  sh1.wdtype = sh2.wdtype = g->dt;  // the shared expert is never an fp8 slot
 }
 
 // MOEINF_STALL_TRACE=<ms>: report (stderr) every forward whose HOST side took longer than <ms>, with the time between

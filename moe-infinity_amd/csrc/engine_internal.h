@@ -120,7 +120,8 @@ static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es)
   return b;
 }
 
-// Device-side (HBM slot) layout: matrices in MFMA-tile order (kernels.hip), biases raw; 4 KiB aligned.
+// Device-side (HBM slot) layout: matrices in MFMA-tile order (kernels.hip), biases raw; 4 KiB aligned.  dt / es: the SLOT's
+// element (DT_F8 / 1 for fp8 slots: 64 k per 1-KiB tile, half of bf16's bytes)
 struct DevLayout {
   int n = 0;
   int64_t off[4] = {0, 0, 0, 0}, size[4] = {0, 0, 0, 0};
@@ -232,6 +233,8 @@ struct moeinf_engine {
   int num_cus = 0;                     // of THIS engine's device
   int layer1_switch_wgs_per_cu = -1;   // occupancy of the one-launch Switch kernel (asked once per engine)
   bool host_f8 = false;                // dtype id 3: fp8 (e4m3fn) experts in the host tier, bf16 slots and arithmetic
+  bool slot_f8 = false;                // ... and fp8 slots (moeinf_create_ex): routed experts stay e4m3fn in HBM, bf16 arithmetic
+  int slot_dt = DT_BF16;               // dtype of the routed experts' slots (DT_F8 with slot_f8, else dt)
   int64_t host_es = 2;                 // bytes per element of the HOST blob (1 with host_f8, else es)
   bool route_v3 = false;               // MOEINF_ROUTER_DEEPSEEK_V3: cfg.router_kind is stored as DEEPSEEK
   std::vector<const float*> gate_bias; // ... per layer: e_score_correction_bias (borrowed device pointers)

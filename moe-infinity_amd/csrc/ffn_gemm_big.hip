@@ -561,6 +561,7 @@ __global__ __launch_bounds__(512) void ffn_gemm_big_kernel(FfnStage s, int nx, i
 
 // max_rows: (an estimate of) the rows of the busiest expert; the kernel's pass loop covers more
 bool launch_ffn_gemm_big(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st) {
+  if (s.wdtype == DT_F8) return false;  // fp8 slots: not built here (the row kernel's fp8 form, kernels.hip)
   if (s.dtype == DT_F32 || (s.K % 64) != 0 || (s.K_sh % 64) != 0 || (s.ld_out % 8) != 0) return false;  // 16-byte row stores
   if ((nmat == 2) != (s.epi == EPI_GATED_SILU)) return false;
   const int rmax = s.R > s.R_sh ? s.R : s.R_sh;

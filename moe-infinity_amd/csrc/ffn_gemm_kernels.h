@@ -515,6 +515,7 @@ __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
 
 template <typename T, int NMAT>
 bool launch_ffn_gemm(const FfnStage& s, dim3 grid, int max_rows, hipStream_t st) {
+  if (s.wdtype == DT_F8) return false;  // fp8 slots: not built here (the row kernel's fp8 form, kernels.hip)
   if (NMAT == 2 && s.epi != EPI_GATED_SILU) return false;  // (the gelu gate: the row kernel, kernels.hip)
   static const int use_gemm = env_int("MOEINF_FFN_GEMM", 2);
   static const int force_nt = env_int("MOEINF_FFN_GEMM_NT", 0);

@@ -223,6 +223,10 @@ struct DT<half_t> {  // fp16 storage
   }
 };
 template <>
+struct DT<uint8_t> {  // fp8 (e4m3fn) SLOT storage, moved as bytes (the pull form of the tier mover; no arithmetic in this dtype)
+  static constexpr int EPV = 16;
+};
+template <>
 struct DT<float> {
   static constexpr int EPV = 4;
   __device__ static __forceinline__ float round(float f) { return f; }
@@ -303,6 +307,32 @@ __device__ __forceinline__ u32x4 ld16_coherent(const void* p) {
 }
 __device__ __forceinline__ u32x4 ld16_nt(const void* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+}
+
+// ---- fp8 weights (fp8 slots, moeinf_create_ex): OCP e4m3fn bytes in the HBM slot, up-cast in registers ----------------------
+// Weight-element tag of the row-dot kernels (ffn_rows_item's WT): the activations stay T (bf16).  An fp8 tile is 16 rows x 64 k in
+// 1 KiB, lane l's 16 bytes = row l & 15, k 16(l >> 4) .. +15 (what pull_retile_kernel<uint8_t, false> writes).
+struct f8w_t {};
+// the fp8 forms' weight load: non-temporal, through the GLOBAL address space (global_load_dwordx4 ... nt; a generic pointer makes it a
+// flat load, which also goes through the flat aperture check)
+__device__ __forceinline__ u32x4 ld16_nt_global(const void* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(reinterpret_cast<uintptr_t>(p)));
+}
+template <bool F8W>
+__device__ __forceinline__ u32x4 ld16_w(const void* p) {
+  if constexpr (F8W) return ld16_nt_global(p);
+  else return ld16_nt(p);
+}
+// the activation type of a kernel instantiated for weight type W (the kernels' first template argument): W itself, bf16 for f8w_t
+template <typename W> struct act_of { using type = W; };
+template <> struct act_of<f8w_t> { using type = uint16_t; };
+// 16 fp8 weights -> two bf16x8 MFMA fragments (k 0..7 and 8..15 of the lane's sixteen): v_cvt_scalef32_pk_bf16_fp8 up-casts two
+// elements per instruction, exactly (e4m3fn -> bf16 loses nothing; gfx950's fp8 is the OCP format torch.float8_e4m3fn holds)
+__device__ __forceinline__ void f8x16_to_bf16(const u32x4 w, u32x4& lo, u32x4& hi) {
+#define CVT(word, sel) __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((word), 1.0f, (sel)))
+  lo = u32x4{CVT(w[0], false), CVT(w[0], true), CVT(w[1], false), CVT(w[1], true)};
+  hi = u32x4{CVT(w[2], false), CVT(w[2], true), CVT(w[3], false), CVT(w[3], true)};
+#undef CVT
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -442,12 +472,17 @@ __device__ __forceinline__ void combine_cols(const CombineArgs& a, const int t, 
 // shared expert's FFN along (gate_shared1_kernel / route_shared2_kernel).
 // COHI / COHO (layer_fused.hip): the activation rows were written / the output rows are read by OTHER workgroups of the same
 // launch — agent-scope loads, write-through stores
-template <typename T, int NMAT, int NW, int U, int NT, bool COHI = false, bool COHO = false>
+// WT: the weight element — T, or f8w_t (fp8 slots: one 16-byte load per lane and matrix per 64-k tile, up-cast in registers to two
+// bf16 fragments, two MFMAs against the lane's 32 contiguous activation bytes at k 16q .. 16q+15: the same k permutation inside the
+// tile on both operands).  fp8 items need K % 64 == 0 (moeinf_create_ex checks): no partial tile.
+template <typename T, int NMAT, int NW, int U, int NT, bool COHI = false, bool COHO = false, typename WT = T>
 __device__ __forceinline__ void ffn_rows_item(const FfnStage& s, const int bx, const char* W, const bool sh, const int cnt, const int off,
                                               float (*red)[NMAT][256], const int xrow_fixed = -1,
                                               const int* in_rows = nullptr, const int* out_rows = nullptr, const EpPeers* pvp = nullptr,
                                               const bool to_peers = false) {
-  constexpr int EPV = DT<T>::EPV;
+  constexpr bool F8W = std::is_same<WT, f8w_t>::value;
+  static_assert(!F8W || std::is_same<T, uint16_t>::value, "fp8 weights run against bf16 activations");
+  constexpr int EPV = F8W ? 16 : DT<T>::EPV;  // weight elements per lane and tile
   constexpr int EPT = 4 * EPV;  // k elements per tile (64 bytes per row)
   const int K = sh ? s.K_sh : s.K;
   const int R = sh ? s.R_sh : s.R;
@@ -492,31 +527,53 @@ __device__ __forceinline__ void ffn_rows_item(const FfnStage& s, const int bx, c
     // wave: 3 round trips instead of 5, 13.7 -> 11.8 us per launch; issuing the first weight batch ahead of the
     // row_map round was measured too and bought nothing)
     for (int kb = wave; kb < KBfull; kb += U * NW) {
-      u32x4 av[U], bv[U], xv[U][NT];
+      u32x4 av[U], bv[U], xv[U][NT], xw[F8W ? U : 1][F8W ? NT : 1];  // xw: the second 16 activation bytes of an fp8 tile
 #pragma unroll
       for (int i = 0; i < U; ++i) {
         if (kb + i * NW < KBfull) {
-          av[i] = ld16_nt(a0 + (size_t)(kb + i * NW) * 1024);
-          if (NMAT == 2) bv[i] = ld16_nt(a1 + (size_t)(kb + i * NW) * 1024);
+          av[i] = ld16_w<F8W>(a0 + (size_t)(kb + i * NW) * 1024);
+          if (NMAT == 2) bv[i] = ld16_w<F8W>(a1 + (size_t)(kb + i * NW) * 1024);
 #pragma unroll
           for (int tt = 0; tt < NT; ++tt)
-            if (tt < ntl) xv[i][tt] = COHI ? ld16_coherent(xr[tt] + (size_t)(kb + i * NW) * EPT) : ld16(xr[tt] + (size_t)(kb + i * NW) * EPT);
+            if (tt < ntl) {
+              if constexpr (F8W) {
+                const T* xp = xr[tt] + (size_t)(kb + i * NW) * EPT;
+                xv[i][tt] = COHI ? ld16_coherent(xp) : ld16(xp);
+                xw[i][tt] = COHI ? ld16_coherent(xp + 8) : ld16(xp + 8);
+              } else {
+                xv[i][tt] = COHI ? ld16_coherent(xr[tt] + (size_t)(kb + i * NW) * EPT) : ld16(xr[tt] + (size_t)(kb + i * NW) * EPT);
+              }
+            }
         }
       }
 #pragma unroll
       for (int i = 0; i < U; ++i) {
         if (kb + i * NW < KBfull) {
+          if constexpr (F8W) {
+            u32x4 a_lo, a_hi, b_lo, b_hi;
+            f8x16_to_bf16(av[i], a_lo, a_hi);
+            if (NMAT == 2) f8x16_to_bf16(bv[i], b_lo, b_hi);
 #pragma unroll
-          for (int tt = 0; tt < NT; ++tt) {
-            if (tt < ntl) {
-              mma16<T>(acc0[tt], av[i], xv[i][tt]);
-              if (NMAT == 2) mma16<T>(acc1[tt], bv[i], xv[i][tt]);
+            for (int tt = 0; tt < NT; ++tt) {
+              if (tt < ntl) {
+                mma16<T>(acc0[tt], a_lo, xv[i][tt]);
+                mma16<T>(acc0[tt], a_hi, xw[i][tt]);
+                if (NMAT == 2) { mma16<T>(acc1[tt], b_lo, xv[i][tt]); mma16<T>(acc1[tt], b_hi, xw[i][tt]); }
+              }
+            }
+          } else {
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) {
+              if (tt < ntl) {
+                mma16<T>(acc0[tt], av[i], xv[i][tt]);
+                if (NMAT == 2) mma16<T>(acc1[tt], bv[i], xv[i][tt]);
+              }
             }
           }
         }
       }
     }
-    if (KB != KBfull && wave == (KBfull % NW)) {  // zero-padded last tile: guard only the activation read
+    if (!F8W && KB != KBfull && wave == (KBfull % NW)) {  // zero-padded last tile: guard only the activation read
       const u32x4 z = {0u, 0u, 0u, 0u};
       const u32x4 w0 = ld16_nt(a0 + (size_t)KBfull * 1024);
       u32x4 w1 = w0;

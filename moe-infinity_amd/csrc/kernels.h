@@ -9,7 +9,10 @@
 namespace moeinf {
 
 enum { DT_BF16 = 0, DT_F32 = 1, DT_F16 = 2 };  // = the reference's dtype ids (core/parallel/expert_module.h:20-23)
-inline int dt_bytes(int dtype) { return dtype == DT_F32 ? 4 : 2; }
+// fp8 (OCP e4m3fn) as the dtype of an HBM SLOT only (fp8 slots, moeinf_create_ex): the weights of routed experts; activations and
+// arithmetic stay bf16.  Never a stage's (activation) dtype.
+constexpr int DT_F8 = 3;
+inline int dt_bytes(int dtype) { return dtype == DT_F32 ? 4 : (dtype == DT_F8 ? 1 : 2); }
 struct EpFuse;
 
 // ---- direct peer-store exchange (expert parallelism without a collective; host side: ep_peer.h) ------------------
@@ -103,6 +106,9 @@ struct FfnStage {
   // LAST block to finish a 16-column tile of y (over all active experts; arrival counter + agent-scope fences)
   // combines those 16 columns for every token, so the combine needs no launch of its own and stays deterministic
   int fuse_combine;
+  // DT_F8: the ROUTED experts' matrices are fp8 tiles (16 rows x 64 k per KiB, up-cast in registers); anything else: `dtype`.  The
+  // shared expert (off_*_sh) is always `dtype`.  (Kept in what was padding in front of tile_done: the struct's size and layout stay.)
+  int wdtype;
   int32_t* tile_done;      // [ceil(R/16)] arrival counters, zero between launches (the last block resets its own)
   CombineArgs comb;
   // batch-1 decode records (self-routing path): written by the meta block of ffn1_selfroute, read by ffn2_decode1
@@ -180,12 +186,13 @@ struct RetileBlob {
   int64_t src_off[4], dst_off[4];
   int R[4], K[4];
   int src_f8;  // pull form only: the source blob holds fp8 (e4m3fn) elements, the slot bf16 (1 source byte per destination element)
+               // (an fp8 SLOT — launch_pull_retile with dtype DT_F8 — copies the bytes as they are: src_f8 = 0)
 };
 hipError_t launch_retile_blob(const RetileBlob& b, int dtype, hipStream_t st);
 // the same from PINNED HOST memory (b.src = device-visible host pointer): the tier mover's pull form, `workgroups` x 256 threads
 // ts: nullptr, or a 4 x u64 timing record in device memory {start tick of the copy's first launch (written when first != 0), max end tick, finished workgroups, -}
 hipError_t launch_pull_retile(const RetileBlob& b, int dtype, int workgroups, hipStream_t st, unsigned long long* ts = nullptr, int first = 1);
-inline int64_t tiled_bytes(int64_t R, int64_t K, int dtype) { const int64_t ept = dtype == DT_F32 ? 16 : 32; return ((R + 15) / 16) * ((K + ept - 1) / ept) * 1024; }
+inline int64_t tiled_bytes(int64_t R, int64_t K, int dtype) { const int64_t ept = dtype == DT_F32 ? 16 : (dtype == DT_F8 ? 64 : 32); return ((R + 15) / 16) * ((K + ept - 1) / ept) * 1024; }
 
 struct RouteArgs {
   const void* x;        // [T,H] dtype x_dtype

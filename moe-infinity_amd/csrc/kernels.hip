@@ -228,7 +228,10 @@ __global__ __launch_bounds__(256) void pull_retile_kernel(RetileBlob b, unsigned
 }
 hipError_t launch_pull_retile(const RetileBlob& b, int dtype, int workgroups, hipStream_t st, unsigned long long* ts, int first) {
   const dim3 grid(workgroups < 1 ? 1 : workgroups);
-  if (b.src_f8) {
+  if (dtype == DT_F8) {  // fp8 slot: fp8 host bytes -> fp8 tiles (16 rows x 64 k per KiB), nothing widened
+    if (b.src_f8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((pull_retile_kernel<uint8_t, false>), grid, dim3(256), 0, st, b, ts, first);
+  } else if (b.src_f8) {
     if (dtype != DT_BF16) return hipErrorInvalidValue;  // fp8 host blobs are up-cast to bf16 slots only
     hipLaunchKernelGGL((pull_retile_kernel<uint16_t, true>), grid, dim3(256), 0, st, b, ts, first);
   } else if (dtype != DT_F32) hipLaunchKernelGGL((pull_retile_kernel<uint16_t, false>), grid, dim3(256), 0, st, b, ts, first);
@@ -243,8 +246,10 @@ hipError_t launch_retile(const void* src, void* dst, int R, int K, int dtype, hi
   return hipGetLastError();
 }
 
+// T = f8w_t: fp8 slots — bf16 activations, the routed experts' weights fp8, a shared expert in the same launch bf16 (e == s.E)
 template <typename T, int NMAT, int NW, int U, int NT>
 __global__ __launch_bounds__(NW * 64) void ffn_rows_kernel(FfnStage s) {
+  using A = typename act_of<T>::type;
   __shared__ float red[NW][NMAT][256];
 
   // Prologue loads in two dependent rounds instead of three: active[u] is fetched together with n_active (entries
@@ -266,7 +271,9 @@ __global__ __launch_bounds__(NW * 64) void ffn_rows_kernel(FfnStage s) {
   if (W == nullptr && threadIdx.x == 0 && blockIdx.x == 0) atomicExch(s.miss_flag, 1);
   const int cnt = W ? cnt_e : 0;
   const int tid = threadIdx.x;
-  ffn_rows_item<T, NMAT, NW, U, NT>(s, blockIdx.x, W, sh, cnt, off, red);
+  if constexpr (std::is_same<A, T>::value) ffn_rows_item<T, NMAT, NW, U, NT>(s, blockIdx.x, W, sh, cnt, off, red);
+  else if (sh) ffn_rows_item<A, NMAT, NW, U, NT>(s, blockIdx.x, W, sh, cnt, off, red);
+  else ffn_rows_item<A, NMAT, NW, U, NT, false, false, T>(s, blockIdx.x, W, sh, cnt, off, red);
   if constexpr (NMAT == 1 && NT == 1) {
     if (s.fuse_combine) {
       // this block's y columns [r0, r0+16) are written; the last of the layer's `nact` blocks to arrive for
@@ -277,7 +284,7 @@ __global__ __launch_bounds__(NW * 64) void ffn_rows_kernel(FfnStage s) {
       if (tid == 0) is_last = (__hip_atomic_fetch_add(&s.tile_done[blockIdx.x], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nact - 1);
       __syncthreads();
       if (is_last) {
-        for (int i = tid; i < s.comb.T * 4; i += NW * 64) combine_cols<T, true>(s.comb, i >> 2, r0 + (i & 3) * 4);
+        for (int i = tid; i < s.comb.T * 4; i += NW * 64) combine_cols<A, true>(s.comb, i >> 2, r0 + (i & 3) * 4);
         if (tid == 0) s.tile_done[blockIdx.x] = 0;
       }
     }
@@ -312,6 +319,18 @@ static void launch_ffn_t(const FfnStage& s, dim3 grid, int nw, int u, bool many_
 #undef LAUNCH
 }
 
+// fp8 slots: the row kernel at every size — the grouped GEMMs are not built for fp8 weights (launch_ffn_gemm* decline such a stage);
+// many rows per expert take the four-token-tile form, one pass over the (half as many) weight bytes per 64 tokens
+template <int NMAT>
+static void launch_ffn_f8w(const FfnStage& s, dim3 grid, int nw, int u, bool many_tokens, hipStream_t st) {
+#define LAUNCH(NWV, UU, NTT) KL((ffn_rows_kernel<f8w_t, NMAT, NWV, UU, NTT>), grid, dim3(NWV * 64), 0, st, s)
+  if (many_tokens) { if (nw == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4); return; }
+  if (nw == 16) { LAUNCH(16, 4, 1); }
+  else if (nw == 8) { if (u == 2) LAUNCH(8, 2, 1); else if (u == 8) LAUNCH(8, 8, 1); else LAUNCH(8, 4, 1); }
+  else         { if (u == 2) LAUNCH(4, 2, 1); else if (u == 8) LAUNCH(4, 8, 1); else LAUNCH(4, 4, 1); }
+#undef LAUNCH
+}
+
 hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, hipStream_t st) {
   static const int env_nw = env_int("MOEINF_FFN_NW", 0), env_u = env_int("MOEINF_FFN_U", 0);
   const int rmax = s.R > s.R_sh ? s.R : s.R_sh;
@@ -319,7 +338,9 @@ hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_
   const bool gated = (s.epi == EPI_GATED_SILU || s.epi == EPI_GATED_GELU);
   // long reductions get 8 waves per block (more bytes in flight per CU), short ones 4
   const int kmax = s.K > s.K_sh ? s.K : s.K_sh;
-  const size_t kbytes = (size_t)kmax * dt_bytes(s.dtype);
+  const bool f8w = s.wdtype == DT_F8;
+  if (f8w && (s.dtype != DT_BF16 || s.K % 64 != 0 || (s.epi != EPI_GATED_SILU && s.epi != EPI_NONE))) return hipErrorInvalidValue;
+  const size_t kbytes = (size_t)kmax * (f8w ? 1 : dt_bytes(s.dtype));  // (routed weight bytes per row)
   // ... and a grid of at most one workgroup per CU (Switch-base-8 at batch 1: 192 / 48 workgroups for 256 CUs) SIXTEEN: a CU
   // that owns a single work item has nothing else to hide its load latency behind, so the whole item goes in flight at
   // once (round 4: stage 2 of Switch-base-8 streamed 9.45 MB in 16.8 us = 0.07 of HBM peak with 48 four-wave workgroups)
@@ -332,7 +353,9 @@ hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_
   // per 128/256 rows) win — Mixtral at 64 tokens: 761 -> 549 us per layer (profiles/r01_ffn_sweep_midsize.txt)
   static const int many_rows = env_int("MOEINF_FFN_MANY_ROWS", 16);
   const bool many = s.fuse_combine ? false : (env_nt ? env_nt > 1 : max_rows_per_expert > many_rows);
-  if (s.dtype == DT_BF16) {
+  if (f8w) {
+    if (gated) launch_ffn_f8w<2>(s, grid, nw, u, many, st); else launch_ffn_f8w<1>(s, grid, nw, u, many, st);
+  } else if (s.dtype == DT_BF16) {
     if (gated) launch_ffn_t<uint16_t, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<uint16_t, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
   } else if (s.dtype == DT_F16) {
     if (gated) launch_ffn_t<half_t, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<half_t, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
@@ -686,8 +709,10 @@ hipError_t launch_route_shared2(const RouteArgs& r, const IndexArgs& a, const Ff
 // per CU spilled 12 bytes per thread = 2 MB of scratch writes per launch, for nothing once four per CU proved best).
 // NMAT = 2: the gated families (Mixtral, DeepSeek); NMAT = 1 (round 4): Switch's plain ReLU experts, top-1 — the same three
 // launches per layer (gate, this, ffn2_decode1) instead of five (gate, route_index, two FFN stages, combine).
+// T = f8w_t (fp8 slots): bf16 activations, the routed items stream fp8 weights, the hidden shared expert's stage 2 stays bf16
 template <typename T, int NMAT, int NW, int U>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(80))) void ffn1_selfroute_kernel(RouteArgs r, IndexArgs a, FfnStage s, FfnStage sh2, int n_rg, int n_sh2) {
+  using A = typename act_of<T>::type;
   __shared__ float red[NW][NMAT][256];
   __shared__ unsigned long long sh_w;
   __shared__ int sh_rank_ok;
@@ -705,7 +730,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(80))) void 
   }
   if (b >= 0 && b < n_sh2) {  // shared expert, stage 2 (h_shared was written by the gate launch)
     const char* Wsh = reinterpret_cast<const char*>(sh2.wptr[sh2.E]);
-    ffn_rows_item<T, 1, NW, U, 1>(sh2, b, Wsh, true, 1, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
+    ffn_rows_item<A, 1, NW, U, 1>(sh2, b, Wsh, true, 1, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
     return;
   }
   b -= n_sh2;
@@ -753,7 +778,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(80))) void 
     return;
   }
   // T == 1: expert-sorted row of (token 0, expert e) = its rank u; the B operand is token 0
-  ffn_rows_item<T, NMAT, NW, U, 1>(s, rg, W, false, 1, u, red, 0);
+  ffn_rows_item<A, NMAT, NW, U, 1, false, false, T>(s, rg, W, false, 1, u, red, 0);
 }
 
 static thread_local hipEvent_t t_timer_start = nullptr, t_timer_stop = nullptr;
@@ -778,6 +803,12 @@ hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const F
   // workgroups, 1.035 -> 1.009 ms/token), 4 for multi-round grids (Mixtral: 1793 workgroups at four per CU)
   static const int sr_u_env = env_int("MOEINF_SR_U", 0);
   const int sr_u = sr_u_env ? sr_u_env : (grid.x > 4 * 256 ? 4 : 8);
+  if (s1.wdtype == DT_F8) {  // fp8 slots (gated families, bf16)
+    if (s1.epi != EPI_GATED_SILU || s1.dtype != DT_BF16) return hipErrorInvalidValue;
+    if (sr_u == 8) KL((ffn1_selfroute_kernel<f8w_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+    else KL((ffn1_selfroute_kernel<f8w_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+    return hipGetLastError();
+  }
   if (s1.epi != EPI_GATED_SILU) {
     // plain experts (Switch, top-1): a grid of at most one workgroup per CU gets sixteen waves per workgroup — the whole
     // work item in flight at once (see launch_ffn_stage)
@@ -807,8 +838,9 @@ hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const F
 // expert, pairs in token order), so stage 2 (the generic kernel, combine fused) finds the rows where the index says they are.
 // grid = 1 + n_sh2 + max_active * n_rg.  Saves the top-k/index launch of decode batches the batcher produces (serving).
 constexpr int SR_MAX_T = 8;
-template <typename T, int NW, int U>
+template <typename T, int NW, int U>  // T = f8w_t: fp8 slots (as ffn1_selfroute_kernel)
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(96))) void ffn1_selfroute_multi_kernel(RouteArgs r, IndexArgs a, FfnStage s, FfnStage sh2, int n_rg, int n_sh2) {
+  using A = typename act_of<T>::type;
   __shared__ float red[NW][2][256];
   __shared__ int s_in[SR_MAX_T];
   __shared__ unsigned long long s_w;
@@ -829,7 +861,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(96))) void 
   }
   if (blk < n_sh2) {  // hidden shared expert, stage 2, all tokens (h_shared was written by the gate launch)
     const char* Wsh = reinterpret_cast<const char*>(sh2.wptr[sh2.E]);
-    ffn_rows_item<T, 1, NW, U, 1>(sh2, blk, Wsh, true, Tn, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
+    ffn_rows_item<A, 1, NW, U, 1>(sh2, blk, Wsh, true, Tn, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
     return;
   }
   blk -= n_sh2;
@@ -876,7 +908,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(96))) void 
     if (threadIdx.x == 0 && rg == 0) atomicExch(s.miss_flag, 1);
     return;
   }
-  ffn_rows_item<T, 2, NW, U, 1>(s, rg, W, false, cnt, s_off, red, -1, s_in, nullptr);
+  ffn_rows_item<A, 2, NW, U, 1, false, false, T>(s, rg, W, false, cnt, s_off, red, -1, s_in, nullptr);
 }
 
 hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, int max_active, hipStream_t st) {
@@ -885,7 +917,11 @@ hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, c
   const dim3 grid(1 + n_sh2 + max_active * n_rg);
   const size_t dyn = grid.x > 4 * 256 ? 30 * 1024 : 0;  // as launch_ffn1_selfroute
 #define SRM(TT, UU) hipLaunchKernelGGL((ffn1_selfroute_multi_kernel<TT, 4, UU>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2)
-  if (s1.dtype == DT_F16) { if (grid.x > 4 * 256) SRM(half_t, 4); else SRM(half_t, 8); }
+  if (s1.wdtype == DT_F8) {  // fp8 slots (bf16)
+    if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
+    if (grid.x > 4 * 256) SRM(f8w_t, 4); else SRM(f8w_t, 8);
+  }
+  else if (s1.dtype == DT_F16) { if (grid.x > 4 * 256) SRM(half_t, 4); else SRM(half_t, 8); }
   else { if (grid.x > 4 * 256) SRM(uint16_t, 4); else SRM(uint16_t, 8); }
 #undef SRM
   return hipGetLastError();
@@ -895,8 +931,9 @@ hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, c
 // form: one scalar round in the prologue (blob pointer dec_w[u] instead of active[u] -> {wptr, counts, offsets}); the
 // combine weights (dec_cw, ascending expert id = rows 0..K-1 of y) are fetched at kernel START, so the last-arriving
 // block's tail is one round of row loads instead of three dependent rounds (order -> slot/weight -> rows).
-template <typename T, int NW, int U>
+template <typename T, int NW, int U>  // T = f8w_t: fp8 slots (bf16 activations, fp8 weights)
 __global__ __launch_bounds__(NW * 64) void ffn2_decode1_kernel(FfnStage s) {
+  using A = typename act_of<T>::type;
   __shared__ float red[NW][1][256];
   __shared__ int is_last;
   const int u = blockIdx.y, tid = threadIdx.x;
@@ -907,7 +944,7 @@ __global__ __launch_bounds__(NW * 64) void ffn2_decode1_kernel(FfnStage s) {
   for (int kk = 0; kk < 8; ++kk) { m.slot[kk] = min(kk, K - 1); m.w[kk] = s.dec_cw[min(kk, K - 1)]; }
   const int r0 = blockIdx.x * 16;
   if (W == nullptr && tid == 0 && blockIdx.x == 0) atomicExch(s.miss_flag, 1);
-  ffn_rows_item<T, 1, NW, U, 1>(s, blockIdx.x, W, false, W ? 1 : 0, u, red);
+  ffn_rows_item<A, 1, NW, U, 1, false, false, T>(s, blockIdx.x, W, false, W ? 1 : 0, u, red);
   wait_stores_acked();  // this thread's (write-through) y stores have reached device-coherent memory
   __syncthreads();
   // (top-1, Switch: this workgroup is the only one of its column tile — no counter to arrive at)
@@ -918,14 +955,14 @@ __global__ __launch_bounds__(NW * 64) void ffn2_decode1_kernel(FfnStage s) {
       if (tid < 4 && r0 + tid * 4 < s.R) {
         const int h0 = r0 + tid * 4;
         float v[4], o[4];
-        DT<T>::unpack4(DT<T>::template fetch4<true>(reinterpret_cast<const T*>(s.comb.y) + h0), v);  // row 0 = (token 0, its expert)
+        DT<A>::unpack4(DT<A>::template fetch4<true>(reinterpret_cast<const A*>(s.comb.y) + h0), v);  // row 0 = (token 0, its expert)
         const float pr = s.comb.router_prob[0];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = DT<T>::round(pr * v[j]);
-        DT<T>::store4(reinterpret_cast<T*>(s.comb.out) + h0, o);
+        for (int j = 0; j < 4; ++j) o[j] = DT<A>::round(pr * v[j]);
+        DT<A>::store4(reinterpret_cast<A*>(s.comb.out) + h0, o);
       }
     } else if (tid < 4) {
-      combine_apply<T, true>(s.comb, 0, r0 + tid * 4, m);
+      combine_apply<A, true>(s.comb, 0, r0 + tid * 4, m);
     }
     if (tid == 0 && K > 1) s.tile_done[blockIdx.x] = 0;
   }
@@ -937,9 +974,13 @@ __global__ __launch_bounds__(NW * 64) void ffn2_decode1_kernel(FfnStage s) {
 // (that tail costs 3.5 us per launch, tools/ffn_micro.hip).  H/16 = 256 workgroups for Mixtral = one per CU.
 // Summation order inside an expert (waves 0..NWE-1, tiles in ascending k inside a wave) and the combine order
 // (ascending expert id) are those of ffn2_decode1_kernel, so the two produce identical bits.  Requires K % 32 == 0.
-template <typename T, int NWE, int U>  // T: uint16_t = bf16, half_t = fp16 (round 5)
+// T = f8w_t (fp8 slots): bf16 activations against 64-k fp8 tiles, the lane's 16 weights up-cast into two fragments against its 32
+// activation bytes (ffn_rows_item's fp8 form); requires K % 64 == 0
+template <typename T, int NWE, int U>  // T: uint16_t = bf16, half_t = fp16 (round 5), f8w_t
 __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStage s) {
-  constexpr int EPT = 32, EPV = 8;
+  using A = typename act_of<T>::type;
+  constexpr bool F8W = std::is_same<T, f8w_t>::value;
+  constexpr int EPT = F8W ? 64 : 32, EPV = F8W ? 16 : 8;
   __shared__ float red[2][NWE][16];
   __shared__ float yv[2][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -954,8 +995,30 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
   }
   const int KB = s.K / EPT;
   const char* a0 = W + s.off_a + (size_t)rg * KB * 1024 + lane * 16;
-  const T* xr = reinterpret_cast<const T*>(s.in) + (size_t)g * s.ld_in + q * EPV;  // T == 1: h row of slot g
+  const A* xr = reinterpret_cast<const A*>(s.in) + (size_t)g * s.ld_in + q * EPV;  // T == 1: h row of slot g
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (F8W) {
+    for (int kb = wl; kb < KB; kb += U * NWE) {
+      u32x4 av[U], xv[U], xw[U];
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        if (kb + i * NWE < KB) {
+          av[i] = ld16_nt_global(a0 + (size_t)(kb + i * NWE) * 1024);
+          xv[i] = ld16(xr + (size_t)(kb + i * NWE) * EPT);
+          xw[i] = ld16(xr + (size_t)(kb + i * NWE) * EPT + 8);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        if (kb + i * NWE < KB) {
+          u32x4 lo, hi;
+          f8x16_to_bf16(av[i], lo, hi);
+          mma16<A>(acc, lo, xv[i]);
+          mma16<A>(acc, hi, xw[i]);
+        }
+      }
+    }
+  } else
   for (int kb = wl; kb < KB; kb += U * NWE) {
     u32x4 av[U], xv[U];
 #pragma unroll
@@ -967,7 +1030,7 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
     }
 #pragma unroll
     for (int i = 0; i < U; ++i)
-      if (kb + i * NWE < KB) mma16<T>(acc, av[i], xv[i]);
+      if (kb + i * NWE < KB) mma16<A>(acc, av[i], xv[i]);
   }
   // every token column of the accumulator holds the same token: lanes n == 0 carry rows q*4 .. q*4+3
   if (n == 0) {
@@ -980,17 +1043,17 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NWE; ++w) v += red[gg][w][row];
-    v = DT<T>::round(v);
+    v = DT<A>::round(v);
     yv[gg][row] = v;
-    if (r0 + row < s.R) DT<T>::store(reinterpret_cast<T*>(s.out) + (size_t)gg * s.ld_out + r0 + row, v);
+    if (r0 + row < s.R) DT<A>::store(reinterpret_cast<A*>(s.out) + (size_t)gg * s.ld_out + r0 + row, v);
   }
   __syncthreads();
   if (tid < 16 && r0 + tid < s.R) {  // combine_apply for one column, ascending expert id (kinds 0 / 1 without a shared expert)
     float p0 = yv[0][tid] * cw0, p1 = yv[1][tid] * cw1;
-    if (s.comb.kind != 1) { p0 = DT<T>::round(p0); p1 = DT<T>::round(p1); }
-    float o = DT<T>::round(0.f + p0);
-    o = DT<T>::round(o + p1);
-    DT<T>::store(reinterpret_cast<T*>(s.comb.out) + r0 + tid, o);
+    if (s.comb.kind != 1) { p0 = DT<A>::round(p0); p1 = DT<A>::round(p1); }
+    float o = DT<A>::round(0.f + p0);
+    o = DT<A>::round(o + p1);
+    DT<A>::store(reinterpret_cast<A*>(s.comb.out) + r0 + tid, o);
   }
 }
 
@@ -1000,6 +1063,22 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
 // against 32.5 us per DeepSeek-V2-Lite layer, profiles/r06_deepseek_stage2_group_forms_rejected.txt — and both are deleted.)
 hipError_t launch_ffn2_decode1(const FfnStage& s2, hipStream_t st) {
   static const int pair_env = env_int("MOEINF_DEC1_PAIR", 1);  // 0: always the arrival-counter form; 4 / 8: waves per expert
+  if (s2.wdtype == DT_F8) {  // fp8 slots (gated families, bf16): the same two forms on fp8 tiles
+    if (s2.dtype != DT_BF16 || s2.comb.kind > 1 || (s2.K % 64) != 0) return hipErrorInvalidValue;
+    static const int pu = env_int("MOEINF_DEC1_PAIR_U", 4);
+    if (pair_env && s2.comb.K == 2 && !(s2.comb.kind == 1 && s2.comb.y_shared)) {
+      const dim3 g1((s2.R + 15) / 16);
+      if (pu == 8) KL((ffn2_decode1_pair_kernel<f8w_t, 4, 8>), g1, dim3(512), 0, st, s2);
+      else KL((ffn2_decode1_pair_kernel<f8w_t, 4, 4>), g1, dim3(512), 0, st, s2);
+      return hipGetLastError();
+    }
+    const dim3 grid((s2.R + 15) / 16, s2.comb.K);
+    static const int du = env_int("MOEINF_DEC1_U", 4);
+    if ((size_t)s2.K >= 16384) KL((ffn2_decode1_kernel<f8w_t, 8, 4>), grid, dim3(512), 0, st, s2);  // (as bf16: by weight bytes per row)
+    else if (du == 8) KL((ffn2_decode1_kernel<f8w_t, 4, 8>), grid, dim3(256), 0, st, s2);
+    else KL((ffn2_decode1_kernel<f8w_t, 4, 4>), grid, dim3(256), 0, st, s2);
+    return hipGetLastError();
+  }
   if (pair_env && (s2.dtype == DT_BF16 || s2.dtype == DT_F16) && s2.comb.K == 2 && (s2.K % 32) == 0 && !(s2.comb.kind == 1 && s2.comb.y_shared) && s2.comb.kind <= 1) {
     const dim3 g1((s2.R + 15) / 16);
     // 4 waves per expert (8 per CU), batches of 4 tiles: 38.9 us per Mixtral launch; 8 waves per expert 40.5; the

@@ -126,9 +126,11 @@ __device__ __forceinline__ const char* layer_selfroute(const RouteArgs& r, const
 // is as cheap, section 4.5 of DESIGN.md): stage 2 + combine stay the launch they were (ffn2_decode1[_pair]).
 // Role = workgroup id (gate first): a workgroup only waits for smaller ids, the dispatcher hands them out in id order.
 // Item bodies = ffn1_selfroute_kernel's / gate_shared1_kernel's (ffn_rows_item<T, 2, 4, U, 1>, gate_body): bit-identical rows.
+// T = f8w_t (fp8 slots): bf16 activations; the routed stage-1 items stream fp8 weights, the gate and the shared expert stay bf16
 template <typename T, typename GW, int U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_front1_kernel(RouteArgs r, IndexArgs a, FfnStage sh1, FfnStage sh2, FfnStage s1, LayerSync sy,
                                                                                               int round_logits, int n_sh1, int n_sh2) {
+  using A = typename act_of<T>::type;
   constexpr int NW = 4;
   __shared__ float red[NW][2][256];
   __shared__ double redg[4][1];
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_
   const int tslot = (int)blockIdx.x * 4;
   layer_trace(sy, tslot + 0);
   if (b < E) {  // ---- gate
-    gate_body<T, GW, 1, true>(reinterpret_cast<const T*>(r.x), reinterpret_cast<const GW*>(r.gate_w), r.logits, 1, r.H, E, round_logits, redg, b, 0);  // (one token: one reduction, not gate_logits_kernel's four)
+    gate_body<A, GW, 1, true>(reinterpret_cast<const A*>(r.x), reinterpret_cast<const GW*>(r.gate_w), r.logits, 1, r.H, E, round_logits, redg, b, 0);  // (one token: one reduction, not gate_logits_kernel's four)
     layer_arrive(sy, LC_GATE);
     layer_trace(sy, tslot + 3);
     return;
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_
   b -= E;
   if (b < n_sh1) {  // ---- shared expert, stage 1 (h_shared is read by THIS launch's shared stage 2: write-through + counter)
     const char* W = reinterpret_cast<const char*>(sh1.wptr[sh1.E]);
-    ffn_rows_item<T, 2, NW, U, 1, false, true>(sh1, b, W, true, 1, 0, red);
+    ffn_rows_item<A, 2, NW, U, 1, false, true>(sh1, b, W, true, 1, 0, red);
     wait_stores_acked();
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_fetch_add(layer_spread_word(sy, LC_SH1, b), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_
       if (threadIdx.x == 0 && rg == 0) atomicExch(s1.miss_flag, 1);
       return;
     }
-    ffn_rows_item<T, 2, NW, U, 1>(s1, rg, W, false, 1, u, red, 0);
+    ffn_rows_item<A, 2, NW, U, 1, false, false, T>(s1, rg, W, false, 1, u, red, 0);
     layer_trace(sy, tslot + 3);
     return;
   }
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_
     const char* W = reinterpret_cast<const char*>(sh2.wptr[sh2.E]);
     layer_wait_spread(sy, LC_SH1, n_sh1);
     layer_trace(sy, tslot + 2);
-    ffn_rows_item<T, 1, NW, U, 1, true, false>(sh2, b, W, true, 1, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
+    ffn_rows_item<A, 1, NW, U, 1, true, false>(sh2, b, W, true, 1, 0, reinterpret_cast<float (*)[1][256]>(&red[0][0][0]));
     layer_trace(sy, tslot + 3);
     (void)n_sh2;
   }
@@ -219,7 +221,11 @@ hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnSt
   const FfnStage& a2 = sh2 ? *sh2 : s1;
 #define F1(TT, GW, UU) KL((moe_front1_kernel<TT, GW, UU>), grid, dim3(256), dyn, st, r, a, a1, a2, s1, sy, rl, n_sh1, n_sh2)
 #define F1U(TT, GW) do { if (sr_u == 8) F1(TT, GW, 8); else F1(TT, GW, 4); } while (0)
-  if (s1.dtype == DT_BF16) { if (r.gate_dtype == DT_BF16) F1U(uint16_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(uint16_t, float); else return hipErrorInvalidValue; }
+  if (s1.wdtype == DT_F8) {  // fp8 slots (bf16)
+    if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
+    if (r.gate_dtype == DT_BF16) F1U(f8w_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(f8w_t, float); else return hipErrorInvalidValue;
+  }
+  else if (s1.dtype == DT_BF16) { if (r.gate_dtype == DT_BF16) F1U(uint16_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(uint16_t, float); else return hipErrorInvalidValue; }
   else if (s1.dtype == DT_F16) { if (r.gate_dtype == DT_F16) F1U(half_t, half_t); else if (r.gate_dtype == DT_F32) F1U(half_t, float); else return hipErrorInvalidValue; }
   else return hipErrorInvalidValue;
 #undef F1U
@@ -372,6 +378,7 @@ int layer1_switch_wgs_per_cu(int x_dtype, int gate_dtype) {
 }
 
 bool launch_moe_layer1_switch(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage& s2, const LayerSync& sy, int num_cus, int wgs_per_cu, hipStream_t st) {
+  if (s1.wdtype == DT_F8 || s2.wdtype == DT_F8) return false;  // (Switch experts never have fp8 slots: moeinf_create_ex refuses them)
   constexpr int KS = 4, P2 = 6, NW = 8;
   const int n_rg = (s1.R + 15) / 16, n_col = (s2.R + 15) / 16;
   const dim3 grid(r.E + 1 + n_rg + KS * n_col);

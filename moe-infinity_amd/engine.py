@@ -63,7 +63,13 @@ class MoEEngine:
             if name == "norm_topk_prob":
                 v = int(bool(v))
             setattr(c, name, v)
-        check(self.lib.moeinf_create(C.byref(c), C.byref(self._h)))
+        if cfg.fp8_slots:
+            opts = _lib.CreateOptions()
+            opts.struct_bytes = C.sizeof(_lib.CreateOptions)
+            opts.slot_dtype = DTYPE_F8E4M3
+            check(self.lib.moeinf_create_ex(C.byref(c), C.byref(opts), C.byref(self._h)))
+        else:
+            check(self.lib.moeinf_create(C.byref(c), C.byref(self._h)))
         self.dtype = _TORCH_DTYPE[cfg.dtype]
         # dtype of the expert blobs in the HOST tier (pack_expert): fp8 experts travel as e4m3fn bytes and are up-cast to bf16 in their slot
         self.host_dtype = torch.float8_e4m3fn if cfg.dtype == DTYPE_F8E4M3 else self.dtype
@@ -73,6 +79,13 @@ class MoEEngine:
         self._moe_forward = self.lib.moeinf_moe_forward
         self._last_T = 0
         self._stores = set()  # OffloadStore objects experts were registered from (kept alive until close())
+
+    @property
+    def slot_dtype(self) -> int:
+        """The dtype id (config.DTYPE_*) the HBM expert slots hold: DTYPE_F8E4M3 with fp8 slots; bf16 for the default fp8 engine."""
+        v = C.c_int32()
+        check(self.lib.moeinf_slot_dtype(self._h, C.byref(v)))
+        return v.value
 
     # ---- lifecycle ---------------------------------------------------------------------------
     def close(self):
