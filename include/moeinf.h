@@ -149,6 +149,11 @@ int moeinf_abi_version(void);
 /* the row estimate moeinf_moe_forward passes to the FFN launchers when every expert of the layer is resident (sync-free path) */
 int moeinf_rows_estimate(int tokens, int top_k, int num_experts);
 int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out5);
+/* Which grouped GEMM an FFN stage of an fp8-slot engine (moeinf_create_ex) takes (csrc/kernels.h f8_gemm_form; arguments as
+ * above, K_sh = 0 when no shared expert rides in the launch).  out[0]: 0 = the row kernel, 1 = ffn_gemm_hyb, 2 = ffn_gemm_lds,
+ * 3 = ffn_gemm_ring2 (their fp8-weight forms); out[1]: waves per workgroup (hyb, lds) or token groups per pass (ring2);
+ * out[2..5]: ring2's split tail, row blocks per expert, first split unit, workgroups (as out[1..4] of moeinf_ffn_ring2_form). */
+int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out6);
 /* The fence ring (csrc/engine_internal.h): sync-free forwards record a fence event only every MOEINF_FENCE_EVERY-th time; a copy
  * that recycles a slot waits for the OLDEST recorded fence that covers the slot's last reader.  moeinf_fence_ring: entries in the
  * ring; moeinf_fence_cover_pos: the ring position that lookup returns (-1: no recorded fence covers `forward` yet) for
@@ -169,8 +174,9 @@ int moeinf_destroy(moeinf_engine* eng);
  * bytes, so about twice the experts per device budget — and the decode FFN kernels stream fp8 weights and up-cast them in
  * registers; activations, gate, shared expert, epilogues and accumulation stay bf16/fp32, so y = FFN(x; W.to(bf16)) as with
  * bf16 slots.  Accepted for Mixtral / DeepSeek experts (routers: Mixtral, softmax-top-k, DeepSeek, DeepSeek-V3), ep_size == 1,
- * hidden % 64 == 0 and inter % 64 == 0; anything else is MOEINF_ERR_UNSUPPORTED with the reason.  Stages with many rows per
- * expert (prefill) run the row kernel's four-token-tile form: the grouped GEMMs are not built for fp8 weights. */
+ * hidden % 64 == 0 and inter % 64 == 0; anything else is MOEINF_ERR_UNSUPPORTED with the reason.  Stages with more than 16
+ * rows per expert (prefill) run fp8-weight forms of the grouped GEMMs (hybrid, LDS-staged, register ring; moeinf_ffn_f8_gemm_form
+ * says which); there is no fp8 form of the 256 x 256 kernel, so above 340 rows per expert the LDS-staged kernel runs. */
 typedef struct moeinf_create_options {
   int32_t struct_bytes;
   int32_t slot_dtype;

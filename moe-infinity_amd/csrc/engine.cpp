@@ -80,6 +80,14 @@ extern "C" int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R
   return MOEINF_OK;
 }
 
+extern "C" int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out6) {
+  if (!out6 || (nmat != 1 && nmat != 2) || K <= 0 || K_sh < 0 || R <= 0 || active <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_ffn_f8_gemm_form: bad arguments");
+  const moeinf::F8GemmForm f = moeinf::f8_gemm_form(nmat, K, K_sh, (R + 15) / 16, active, max_rows, num_cus, moeinf::F8GemmKnobs());
+  out6[0] = f.kernel; out6[1] = f.width;
+  out6[2] = f.ring.tail; out6[3] = f.ring.nblk; out6[4] = f.ring.split; out6[5] = f.ring.blocks;
+  return MOEINF_OK;
+}
+
 // OCP e4m3fn (torch.float8_e4m3fn: 1-4-3, bias 7, no infinities, S.1111.111 = NaN) -> bf16 bits; exact (3 mantissa bits)
 static inline uint16_t f8e4m3_to_bf16_bits(uint8_t v) {
   const uint32_t s = v >> 7, ex = (v >> 3) & 15, m = v & 7;

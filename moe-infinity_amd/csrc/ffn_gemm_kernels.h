@@ -15,6 +15,10 @@ namespace moeinf {
 // ffn_gemm_ring2.hip: the register-ring kernel, launched when ring2_form (kernels.h) picks one of its forms; false: not handled
 bool launch_ffn_gemm_ring2_bf16(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);
 
+// fp8-slot bodies (T = f8w_t): ffn_gemm_f8_kernels.h
+template <int NMAT, int RGB, int NWV, bool XL> __device__ __forceinline__ void ffn_gemm_lds_kernel_f8w(const FfnStage& s);
+template <int NMAT, int RW, int KK, bool XL> __device__ __forceinline__ void ffn_gemm_hyb_kernel_f8w(const FfnStage& s);
+
 // ------------------------------------------------------------------------------------------------
 // ffn_gemm: the same stage for experts with MANY tokens (prefill, large batches) — a register-tiled
 // grouped GEMM on MFMA.  A block owns RG row groups (16*RG weight rows, for the gated stage of BOTH
@@ -189,6 +193,9 @@ __global__ __launch_bounds__(NW * 64) void ffn_gemm_kernel(FfnStage s) {
 // at 512 tokens, 808 -> 970-1005 us at 2048; DeepSeek +-10 % either way.  Not kept.)
 template <typename T, int NMAT, int RGB, int NWV, bool XL>
 __global__ __launch_bounds__(NWV * 64) void ffn_gemm_lds_kernel(FfnStage s) {
+  if constexpr (std::is_same<T, f8w_t>::value) {  // fp8 slots (ffn_gemm_f8_kernels.h, built by ffn_gemm_f8.hip)
+    ffn_gemm_lds_kernel_f8w<NMAT, RGB, NWV, XL>(s);
+  } else {
   constexpr int EPV = DT<T>::EPV;
   constexpr int EPT = 4 * EPV;
   constexpr int RGW = RGB / 2;
@@ -346,6 +353,7 @@ __global__ __launch_bounds__(NWV * 64) void ffn_gemm_lds_kernel(FfnStage s) {
     });
     __syncthreads();  // the next pass re-uses buffer 0
   }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -365,6 +373,9 @@ __global__ __launch_bounds__(NWV * 64) void ffn_gemm_lds_kernel(FfnStage s) {
 //   an even number of k-tiles).
 template <typename T, int NMAT, int RW, int KK, bool XL>
 __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
+  if constexpr (std::is_same<T, f8w_t>::value) {  // fp8 slots (ffn_gemm_f8_kernels.h, built by ffn_gemm_f8.hip)
+    ffn_gemm_hyb_kernel_f8w<NMAT, RW, KK, XL>(s);
+  } else {
   static_assert(!XL || KK % 2 == 0, "full-line staging moves k-tiles in pairs");
   constexpr int EPV = DT<T>::EPV;
   constexpr int EPT = 4 * EPV;
@@ -510,6 +521,7 @@ __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
       }
     });
     __syncthreads();  // the next pass re-uses LDS buffer 0
+  }
   }
 }
 

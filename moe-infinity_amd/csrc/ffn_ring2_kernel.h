@@ -77,8 +77,9 @@ __device__ __forceinline__ void frag_wait(u32x4 (&f)[CW]) {
 
 template <int WL, int N>
 __device__ __forceinline__ void ring2_wait(u32x4 (&w)[WL]) {
-  static_assert(WL == 2 || WL == 4, "2 or 4 weight tiles per stage");
-  if constexpr (WL == 4) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N) : "memory");
+  static_assert(WL == 1 || WL == 2 || WL == 4, "1, 2 or 4 weight tiles per stage (1 / 2: fp8 tiles, 64 k each)");
+  if constexpr (WL == 1) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w[0]) : "n"(N) : "memory");
+  else if constexpr (WL == 4) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N) : "memory");
   else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[0]), "+v"(w[1]) : "n"(N) : "memory");
 }
 
@@ -87,11 +88,16 @@ __device__ __forceinline__ void ring2_wait(u32x4 (&w)[WL]) {
 // vs 359.8-384.4 us for this form, 384 / 768 tokens within 1 % — no gain for 24 KiB more LDS, so it was removed.)
 template <typename T, int NMAT, int NTB, int D, bool TAIL = false>
 __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
-  static_assert(sizeof(T) == 2, "bf16 / fp16");
+  // T = f8w_t (fp8 slots, ffn_gemm_f8.hip): bf16 activations (A); a stage's 64 k are ONE fp8 tile per matrix (WL = NMAT), up-cast
+  // into the fragments of both k-tiles when the stage is consumed.  Routed experts only: the launcher never gives this form a
+  // shared expert (its weights are bf16)
+  using A = typename act_of<T>::type;
+  constexpr bool F8 = std::is_same<T, f8w_t>::value;
+  static_assert(sizeof(A) == 2, "bf16 / fp16");
   static_assert(D >= 3 && D <= 6, "register ring of 3..6 stages");
   static_assert(NTB % 4 == 0, "whole activation DMA pieces per wave");
   constexpr int NWV = 8, KT = 2, EPT = 32, EPV = 8;
-  constexpr int WL = KT * NMAT;             // weight tiles (1 KiB) per wave and stage
+  constexpr int WL = F8 ? NMAT : KT * NMAT;  // weight tiles (1 KiB) per wave and stage
   constexpr int XSTAGE = KT * NTB * 1024;   // activation bytes per stage
   constexpr int NX = 3;                       // LDS ring
   constexpr int CW = 8 / NMAT;              // token groups per chunk: 8 MFMAs between two fragment batches
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
   const int n = lane & 15, q = lane >> 4;
   const int KB = K / EPT;
   const int KS = KB / KT;
-  const size_t rg_stride = (size_t)KB * 1024;
+  const size_t rg_stride = (size_t)(F8 ? KB / 2 : KB) * 1024;
   // this wave's weight-tile stream(s) (a row group past the end re-reads the last one; its results are dropped)
   // (a half workgroup: waves 0-3 own row groups half*4 .. half*4+3 of the block, waves 4-7 only keep the barriers company)
   const int rg_want = bx * NWV + (half > 0 ? 4 : 0) + wave;
@@ -141,7 +147,8 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
   uint32_t frag_off[KT];
 #pragma unroll
-  for (int kk = 0; kk < KT; ++kk) frag_off[kk] = (n >> 3) * 1024 + rr * 128 + ((((kk & 1) * 4 + q) ^ rr) << 4);
+  // (fp8: the lane's 16 weights of a stage are k 16q .. 16q+15, their bf16 halves meet chunks 2q (kk = 0) and 2q+1 (kk = 1))
+  for (int kk = 0; kk < KT; ++kk) frag_off[kk] = (n >> 3) * 1024 + rr * 128 + (((F8 ? 2 * q + kk : (kk & 1) * 4 + q) ^ rr) << 4);
 
   for (int tile0 = 0; tile0 * 16 < cnt; tile0 += NTB) {
     const int ntl = min(NTB, (cnt - tile0 * 16 + 15) / 16);  // token groups present in this pass (block-uniform)
@@ -177,10 +184,10 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
       u32x4 wr[D][WL];  // [ring stage][k-tile * NMAT + matrix]
       auto issue_w1 = [&](int ks, u32x4 (&dst)[WL], int t) {  // past the end: re-read the last stage (never multiplied)
         const int kk = t / NMAT, m = t % NMAT;
-        ring_load(dst[t], ap[m] + (size_t)(min(ks, KS - 1) * KT + kk) * 1024);
+        ring_load(dst[t], ap[m] + (size_t)(F8 ? min(ks, KS - 1) : min(ks, KS - 1) * KT + kk) * 1024);
       };
       auto issue_x1 = [&](int ks, int i) {
-        __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const T*>(s.in) + ((size_t)xoff[i] + (size_t)min(ks, KS - 1) * KT * EPT)),
+        __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const A*>(s.in) + ((size_t)xoff[i] + (size_t)min(ks, KS - 1) * KT * EPT)),
                                          (lptr_t)(smem + (ks % NX) * XSTAGE + (wave + NWVE * i) * 1024), 16, 0, 0);
       };
       // Issue order of every wave: prologue W0 X0 W1 X1 W2 .. W(D-2); step S issues X(S+2) then W(S+D-1), spread over its
@@ -200,6 +207,11 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
         for (int t = 0; t < WL; ++t) issue_w1(d, wr[d], t);
       auto step = [&](int S, u32x4 (&wc)[WL], u32x4 (&wn)[WL]) {
         ring2_wait<WL, NWAIT>(wc);      // this wave's W(S) and X(S) landed
+        u32x4 wlo[F8 ? NMAT : 1], whi[F8 ? NMAT : 1];  // fp8: the stage's tiles up-cast, k-tile 0 / 1 halves
+        if constexpr (F8) {
+#pragma unroll
+          for (int m = 0; m < NMAT; ++m) f8x16_to_bf16(wc[m], wlo[m], whi[m]);
+        }
         __builtin_amdgcn_s_barrier();   // everybody's X(S) landed; the LDS buffer the step refills and ring slot (S-1)%D are free
         const uint32_t sbase = lds0 + (S % NX) * XSTAGE;
         uint32_t fa[KT];
@@ -232,7 +244,10 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
           static_for<width>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
 #pragma unroll
-            for (int m = 0; m < NMAT; ++m) mma16<T>(acc[c * CW + i][m], wc[kk * NMAT + m], fb[j & 1][i]);
+            for (int m = 0; m < NMAT; ++m) {
+              if constexpr (F8) mma16<A>(acc[c * CW + i][m], kk == 0 ? wlo[m] : whi[m], fb[j & 1][i]);
+              else mma16<A>(acc[c * CW + i][m], wc[kk * NMAT + m], fb[j & 1][i]);
+            }
           });
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -250,14 +265,14 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
       // epilogue straight from the accumulators: lane holds 4 consecutive rows of one token
       epi_switch<NMAT>(s.epi, [&](auto epic) {
         constexpr int EPI = decltype(epic)::value;
-        const T* bias = reinterpret_cast<const T*>(W + s.off_bias);
+        const A* bias = reinterpret_cast<const A*>(W + s.off_bias);
         const bool aligned = (s.ld_out & 3) == 0;
 #pragma unroll
         for (int b = 0; b < NG; ++b) {
           const int tok = (tile0 + b) * 16 + n;
           if (tok < cnt && rg_live) {
             const int srow = s.out_map ? s.out_map[off + tok] : off + tok;
-            epi_quad<T, EPI>(acc[b][0], acc[b][NMAT - 1], bias, rg * 16 + q * 4, R, aligned, reinterpret_cast<T*>(s.out) + (size_t)srow * s.ld_out);
+            epi_quad<A, EPI>(acc[b][0], acc[b][NMAT - 1], bias, rg * 16 + q * 4, R, aligned, reinterpret_cast<A*>(s.out) + (size_t)srow * s.ld_out);
           }
         }
       });

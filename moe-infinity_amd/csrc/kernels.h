@@ -173,6 +173,41 @@ inline Ring2Form ring2_form(int elem_bytes, bool f16, int nmat, int K, int K_sh,
   return f;
 }
 
+// ---- which grouped GEMM an fp8-slot stage takes (ffn_gemm_f8.hip): pure host logic, shared by launch_ffn_gemm_f8 and the export
+// moeinf_ffn_f8_gemm_form (engine.cpp), pinned by tests/test_fp8_gemm_selection_cpu.py against DESIGN.md section 4.3.  The bf16
+// thresholds and knobs, without the 256 x 256 kernel (not built for fp8): above ring2's rows the LDS-staged kernel's 8-wave form.
+struct F8GemmKnobs {
+  Ring2Knobs ring = Ring2Knobs::from_env();
+  int use_gemm = Ring2Knobs::env_or("MOEINF_FFN_GEMM", 2);         // 0: the row kernel's four-token-tile form; 3: always hybrid
+  int many_rows = Ring2Knobs::env_or("MOEINF_FFN_MANY_ROWS", 16);  // up to here: the row kernel (decode)
+  int wide = Ring2Knobs::env_or("MOEINF_GEMM_WIDE", -1);           // ffn_gemm_lds 8 waves (-1: above 128 rows)
+};
+enum { F8G_ROWS = 0, F8G_HYB = 1, F8G_LDS = 2, F8G_RING2 = 3 };
+struct F8GemmForm {
+  int kernel = F8G_ROWS;
+  int width = 0;   // hyb / lds: waves per workgroup; ring2: token groups per pass (ring.ntb)
+  Ring2Form ring;  // kernel == F8G_RING2
+};
+// K_sh: the shared expert's reduction length, 0 without a shared expert in the launch (its weights are bf16: the hybrid and LDS
+// kernels give its workgroups the bf16 body; ring2's fp8 form takes routed experts only)
+inline F8GemmForm f8_gemm_form(int nmat, int K, int K_sh, int row_groups, int active, int max_rows, int num_cus, const F8GemmKnobs& k) {
+  F8GemmForm f;
+  if (max_rows <= k.many_rows || k.use_gemm == 0 || K % 64 != 0 || K_sh % 32 != 0) return f;
+  if (k.use_gemm != 3) {
+    if (K_sh == 0) {
+      f.ring = ring2_form(2, false, nmat, K, K_sh, row_groups, active, max_rows, num_cus, k.ring);
+      if (f.ring.ntb) { f.kernel = F8G_RING2; f.width = f.ring.ntb; return f; }
+    }
+    if (max_rows > hyb_rows_for(active, k.ring)) {
+      f.kernel = F8G_LDS;
+      f.width = (k.wide >= 0 ? k.wide != 0 : max_rows > 128) ? 8 : 4;
+      return f;
+    }
+  }
+  f.kernel = F8G_HYB; f.width = 4;
+  return f;
+}
+
 // max_rows_per_expert: upper bound of rows any one expert receives (selects the multi-token-tile variant)
 hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, hipStream_t st);
 // row-major [R,K] -> MFMA A-operand tiles (see kernels.hip); dst needs tiled_bytes(R,K) bytes

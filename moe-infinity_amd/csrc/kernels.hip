@@ -319,12 +319,19 @@ static void launch_ffn_t(const FfnStage& s, dim3 grid, int nw, int u, bool many_
 #undef LAUNCH
 }
 
-// fp8 slots: the row kernel at every size — the grouped GEMMs are not built for fp8 weights (launch_ffn_gemm* decline such a stage);
-// many rows per expert take the four-token-tile form, one pass over the (half as many) weight bytes per 64 tokens
+bool launch_ffn_gemm_f8(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);  // ffn_gemm_f8.hip
+
+// fp8 slots: up to 16 rows per expert the row kernel; more rows take the fp8 forms of the grouped GEMMs (ffn_gemm_f8.hip, chosen by
+// f8_gemm_form).  The row kernel's four-token-tile form is left for what they decline: MOEINF_FFN_GEMM=0 (as for bf16), a
+// shared expert whose reduction is not a multiple of 32, a forced MOEINF_FFN_NT with <= 16 rows
 template <int NMAT>
-static void launch_ffn_f8w(const FfnStage& s, dim3 grid, int nw, int u, bool many_tokens, hipStream_t st) {
+static void launch_ffn_f8w(const FfnStage& s, dim3 grid, int nw, int u, bool many_tokens, int max_rows, hipStream_t st) {
 #define LAUNCH(NWV, UU, NTT) KL((ffn_rows_kernel<f8w_t, NMAT, NWV, UU, NTT>), grid, dim3(NWV * 64), 0, st, s)
-  if (many_tokens) { if (nw == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4); return; }
+  if (many_tokens) {
+    if (launch_ffn_gemm_f8(s, NMAT, grid, max_rows, st)) return;
+    if (nw == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4);
+    return;
+  }
   if (nw == 16) { LAUNCH(16, 4, 1); }
   else if (nw == 8) { if (u == 2) LAUNCH(8, 2, 1); else if (u == 8) LAUNCH(8, 8, 1); else LAUNCH(8, 4, 1); }
   else         { if (u == 2) LAUNCH(4, 2, 1); else if (u == 8) LAUNCH(4, 8, 1); else LAUNCH(4, 4, 1); }
@@ -354,7 +361,7 @@ hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_
   static const int many_rows = env_int("MOEINF_FFN_MANY_ROWS", 16);
   const bool many = s.fuse_combine ? false : (env_nt ? env_nt > 1 : max_rows_per_expert > many_rows);
   if (f8w) {
-    if (gated) launch_ffn_f8w<2>(s, grid, nw, u, many, st); else launch_ffn_f8w<1>(s, grid, nw, u, many, st);
+    if (gated) launch_ffn_f8w<2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_f8w<1>(s, grid, nw, u, many, max_rows_per_expert, st);
   } else if (s.dtype == DT_BF16) {
     if (gated) launch_ffn_t<uint16_t, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<uint16_t, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
   } else if (s.dtype == DT_F16) {

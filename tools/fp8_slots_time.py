@@ -6,11 +6,13 @@ process of its own.  Legs:
     decode-deepseek    DeepSeek-V2-Lite, 26 layers resident, batch 1: ms/token
     miss-mixtral       Mixtral-8x7B, 16 layers, device_memory_bytes = 50 % of the layers' bf16 expert bytes, changing routing:
                        hit rate once warm and ms/token
-    prefill-mixtral    Mixtral-8x7B, 8 layers resident, 512 tokens: ms per layer
-    prefill-deepseek   DeepSeek-V2-Lite, 8 layers resident, 512 tokens: ms per layer
+    prefill-mixtral    Mixtral-8x7B, 8 layers resident, 512 tokens (--tokens): ms per layer
+    prefill-deepseek   DeepSeek-V2-Lite, 8 layers resident, 512 tokens (--tokens): ms per layer
 
-    python tools/fp8_slots_time.py [leg ...]          (default: every leg; one JSON line per run, then a summary)
-    python tools/fp8_slots_time.py --child <leg> <0|1> [--steps N]   (one run; used by the above and by rocprofv3)
+    python tools/fp8_slots_time.py [--tokens N,...] [--trees DIR,...] [leg ...]
+        (default: every leg; one JSON line per run, then a summary.  --tokens: the prefill legs at each length; --trees: the
+        same runs against the library of each of these checkouts in turn, A/B/A/B — e.g. the parent commit and this one)
+    python tools/fp8_slots_time.py --child <leg> <0|1> [--steps N] [--tokens N] [--tree DIR]   (one run; used by the above and by rocprofv3)
 """
 import json
 import os
@@ -22,14 +24,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEGS = ["decode-mixtral", "decode-deepseek", "miss-mixtral", "prefill-mixtral", "prefill-deepseek"]
 
 
-def child(leg, fp8_slots, steps):
-    sys.path.insert(0, ROOT)
+def child(leg, fp8_slots, steps, tokens=512, tree=ROOT):
+    sys.path.insert(0, tree)
     import torch
     from moe_infinity_amd import MoEEngine
     from moe_infinity_amd import config as Cf
 
     wl = "mixtral" if "mixtral" in leg else "deepseek"
-    T = 512 if leg.startswith("prefill") else 1
+    T = tokens if leg.startswith("prefill") else 1
     mk = Cf.mixtral_8x7b if wl == "mixtral" else Cf.deepseek_v2_lite
     cfg = mk(dtype=Cf.DTYPE_F8E4M3, gate_dtype=Cf.DTYPE_BF16, max_tokens=T, fp8_slots=bool(fp8_slots), device_memory_ratio=0.8)
     if leg == "miss-mixtral":
@@ -98,32 +100,49 @@ def child(leg, fp8_slots, steps):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def main(legs):
+def main(legs, tokens=(512,), trees=(ROOT,)):
     steps = {"decode-mixtral": 40, "decode-deepseek": 60, "miss-mixtral": 10, "prefill-mixtral": 3, "prefill-deepseek": 5}
+    runs = [(leg, t) for leg in legs for t in (tokens if leg.startswith("prefill") else (1,))]
     rows = []
     for rnd in range(2):  # A/B/A/B
-        for leg in legs:
+        for leg, t in runs:
+            for tree in trees:
+                for f8 in (0, 1):
+                    st = max(1, steps[leg] * 512 // t) if leg.startswith("prefill") else steps[leg]
+                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", leg, str(f8), "--steps", str(st), "--tokens", str(t),
+                                        "--tree", tree], capture_output=True, text=True, timeout=900)
+                    r = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+                    if p.returncode != 0 or not r:
+                        print(f"{leg} fp8_slots={f8} tree={tree}: exit {p.returncode}\n{p.stderr[-2000:]}", flush=True)
+                        sys.exit(1)  # a failed GPU run ends the measurement
+                    d = json.loads(r[0][7:])
+                    d.update(round=rnd, tree=os.path.basename(os.path.abspath(tree)))
+                    rows.append(d)
+                    print(json.dumps(d), flush=True)
+    for leg, t in runs:
+        for tree in trees:
             for f8 in (0, 1):
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", leg, str(f8), "--steps", str(steps[leg])],
-                                   capture_output=True, text=True, timeout=900)
-                r = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
-                if p.returncode != 0 or not r:
-                    print(f"{leg} fp8_slots={f8}: exit {p.returncode}\n{p.stderr[-2000:]}", flush=True)
-                    sys.exit(1)  # a failed GPU run ends the measurement
-                d = json.loads(r[0][7:])
-                d["round"] = rnd
-                rows.append(d)
-                print(json.dumps(d), flush=True)
-    for leg in legs:
-        for f8 in (0, 1):
-            rs = [r for r in rows if r["leg"] == leg and r["fp8_slots"] == f8]
-            key = "ms_per_token" if "ms_per_token" in rs[0] else "ms_per_layer"
-            extra = f" hit_rate {[r['hit_rate'] for r in rs]}" if "hit_rate" in rs[0] else ""
-            print(f"SUMMARY {leg:18s} {'fp8 slots ' if f8 else 'bf16 slots'} {key} {[r[key] for r in rs]}{extra}", flush=True)
+                name = os.path.basename(os.path.abspath(tree))
+                rs = [r for r in rows if r["leg"] == leg and r["fp8_slots"] == f8 and r["tree"] == name and (r.get("tokens", 1) == t or leg.startswith(("decode", "miss")))]
+                key = "ms_per_token" if "ms_per_token" in rs[0] else "ms_per_layer"
+                extra = f" hit_rate {[r['hit_rate'] for r in rs]}" if "hit_rate" in rs[0] else ""
+                tt = f" T={t}" if leg.startswith("prefill") else ""
+                print(f"SUMMARY {leg:18s}{tt:7s} {name:10s} {'fp8 slots ' if f8 else 'bf16 slots'} {key} {[r[key] for r in rs]}{extra}", flush=True)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        child(sys.argv[2], int(sys.argv[3]), int(sys.argv[5]) if len(sys.argv) > 5 else 20)
+    args = sys.argv[1:]
+
+    def opt(name, default):
+        if name in args:
+            i = args.index(name)
+            v = args[i + 1]
+            del args[i:i + 2]
+            return v
+        return default
+
+    steps_, tokens_, tree_, trees_ = opt("--steps", "20"), opt("--tokens", "512"), opt("--tree", ROOT), opt("--trees", ROOT)
+    if args and args[0] == "--child":
+        child(args[1], int(args[2]), int(steps_), int(tokens_), os.path.abspath(tree_))
     else:
-        main([a for a in sys.argv[1:]] or LEGS)
+        main(args or LEGS, [int(t) for t in tokens_.split(",")], [os.path.abspath(t) for t in trees_.split(",")])
