@@ -229,6 +229,16 @@ int moeinf_register_shared(moeinf_engine* eng, int layer, const void* blob, int6
 #define MOEINF_FWD_NO_COMBINE 2u  /* stop after the expert FFN (parity tests) */
 int moeinf_moe_forward(moeinf_engine* eng, int layer, const void* x_dev, int tokens, int batch_rows,
                        const void* gate_w_dev, void* out_dev, void* stream, uint32_t flags);
+/* moeinf_moe_forward with a per-token mask (padded batches: HF NLLB-MoE's padding_mask, left-padded prompts).
+ * token_mask_dev: [tokens] bytes on the device, non-zero = real token, 0 = masked; NULL = moeinf_moe_forward exactly.
+ * A masked token is a token whose every routed pair the router dropped: it takes no expert, no capacity (Switch's per-row
+ * priority counts real tokens only) and never causes a fetch, a prefetch or a tracer record; its output row is the
+ * family's no-pair rule (Mixtral / Grok: 0, DeepSeek: the shared expert alone, Switch: router_prob * x, NLLB: x).
+ * Routing reports show its pairs as dropped ones (index -1, weight 0); expert counts, hits and misses count real pairs.
+ * ep_size > 1 with a mask: MOEINF_ERR_UNSUPPORTED, nothing enqueued. */
+int moeinf_moe_forward_masked(moeinf_engine* eng, int layer, const void* x_dev, int tokens, int batch_rows,
+                              const void* gate_w_dev, void* out_dev, void* stream, uint32_t flags,
+                              const uint8_t* token_mask_dev);
 
 /* expert_dispatcher.set_inputs + enqueue_expert(...) for every active expert + wait_expert
  * (core/parallel/expert_dispatcher.cpp:111-158,436-450; driven by dispatch_local,

@@ -97,6 +97,7 @@ PROTOTYPES = {
     "moeinf_expert_host_ptr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "moeinf_register_shared": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "moeinf_moe_forward": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_uint32]),
+    "moeinf_moe_forward_masked": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_uint32, _P]),
     "moeinf_dispatch_mask": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _I32P, _I32P, _P]),
     "moeinf_dispatch_mask_subset": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _I32P, _I32P, _P, _I32P, C.c_int]),
     "moeinf_copy_routing_dev": (C.c_int, [_P, _P, _P, _P, _P]),

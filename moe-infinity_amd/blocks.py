@@ -49,10 +49,11 @@ class _MoeBlockBase(nn.Module):
     def _gate_weight(self) -> torch.Tensor:
         raise NotImplementedError
 
-    def _run(self, hidden_states: torch.Tensor, batch_rows: int = 1) -> torch.Tensor:
+    def _run(self, hidden_states: torch.Tensor, batch_rows: int = 1, token_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.engine is None:
             raise RuntimeError("attach_engine() first: the block has no CPU/PyTorch fallback")
-        out = self.engine.forward(self.layer_id, hidden_states.contiguous(), self._gate_weight(), batch_rows=batch_rows)
+        out = self.engine.forward(self.layer_id, hidden_states.contiguous(), self._gate_weight(), batch_rows=batch_rows,
+                                  token_mask=token_mask)
         if self.expert_predictor is not None and self.expert_prefetcher is not None and self.seq_id_list:
             # mixtral.py:71-85 (commented out in the reference): predict + prefetch per sequence
             r = self.engine.routing()
@@ -189,6 +190,19 @@ class SyncSwitchTransformersSparseMLP(_MoeBlockBase):
                                expert_capacity=config.expert_capacity, **kw)
 
 
+def nllb_non_padding(padding_mask: torch.Tensor, nb_tokens: int) -> torch.Tensor:
+    """HF NllbMoeTop2Router.route_tokens' reduction of ``padding_mask`` (the attention mask the encoder / decoder layer hands
+    its ffn) to one flag per token, True = routed: a 4-D mask keeps the last query row of each batch entry and then the
+    last ``nb_tokens`` entries (the decoder's quirk, kept as HF has it), and ``non_padding = ~padding_mask.bool()``.
+    Returns bool [nb_tokens] on the mask's device."""
+    if padding_mask.dim() == 4:
+        padding_mask = padding_mask[:, :, -1, :].reshape(-1)[-nb_tokens:]
+    non_padding = ~padding_mask.bool()
+    if non_padding.numel() != nb_tokens:
+        raise ValueError(f"padding_mask reduces to {non_padding.numel()} flags for {nb_tokens} tokens")
+    return non_padding.reshape(nb_tokens)
+
+
 class SyncNllbMoeSparseMLP(_MoeBlockBase):
     def __init__(self, config, ffn_dim: int):
         super().__init__()
@@ -196,19 +210,28 @@ class SyncNllbMoeSparseMLP(_MoeBlockBase):
         self.router.classifier = nn.Linear(config.d_model, config.num_experts, bias=False)
         self.num_experts = config.num_experts
         self.ffn_dim = ffn_dim
+        self.router_ignore_padding_tokens = bool(getattr(config, "router_ignore_padding_tokens", False))
 
     def _gate_weight(self):
         return self.router.classifier.weight
 
     def forward(self, hidden_states: torch.Tensor, padding_mask: Optional[torch.Tensor] = None):
-        if padding_mask is not None:
-            raise NotImplementedError("padding_mask routing is not part of the built path")
-        out = self._run(hidden_states)
+        non_padding = None
+        if padding_mask is not None and not self.router_ignore_padding_tokens:
+            non_padding = nllb_non_padding(padding_mask, hidden_states.numel() // hidden_states.shape[-1]).to(hidden_states.device)
+        out = self._run(hidden_states, token_mask=non_padding)
         _, idx, w = self.engine.routing_tensors(logits=False, topk=True)
         t = idx.shape[0]
         router_probs = torch.zeros((t, self.num_experts), dtype=hidden_states.dtype, device=hidden_states.device)
-        router_probs.scatter_(1, idx.long(), w.to(hidden_states.dtype))  # combining weights [T,E]
-        return out, (router_probs, idx[:, 0].long())
+        if non_padding is None:
+            router_probs.scatter_(1, idx.long(), w.to(hidden_states.dtype))  # combining weights [T,E]
+            return out, (router_probs, idx[:, 0].long())
+        # pad rows (route_tokens zeroes their top-1 / top-2 masks): every pair dropped (-1, weight 0) -> an all-zero
+        # router_probs row and top-1 index argmax(0-row) = 0
+        keep = idx >= 0
+        router_probs.scatter_add_(1, idx.long().clamp_min(0), torch.where(keep, w, torch.zeros_like(w)).to(hidden_states.dtype))
+        top1 = torch.where(non_padding, idx[:, 0].long(), torch.zeros_like(idx[:, 0], dtype=torch.long))
+        return out, (router_probs, top1)
 
     @staticmethod
     def engine_config(config, ffn_dim, num_layers, **kw) -> Cf.EngineConfig:

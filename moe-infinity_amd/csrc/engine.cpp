@@ -1613,8 +1613,22 @@ struct StallTrace {
   }
 };
 
+static int moe_forward(moeinf_engine* g, int layer, const void* x_dev, int tokens, int batch_rows, const void* gate_w_dev,
+                       void* out_dev, void* stream, uint32_t flags, const uint8_t* token_mask);
 extern "C" int moeinf_moe_forward(moeinf_engine* g, int layer, const void* x_dev, int tokens, int batch_rows, const void* gate_w_dev,
                                   void* out_dev, void* stream, uint32_t flags) {
+  return moe_forward(g, layer, x_dev, tokens, batch_rows, gate_w_dev, out_dev, stream, flags, nullptr);
+}
+extern "C" int moeinf_moe_forward_masked(moeinf_engine* g, int layer, const void* x_dev, int tokens, int batch_rows, const void* gate_w_dev,
+                                         void* out_dev, void* stream, uint32_t flags, const uint8_t* token_mask_dev) {
+  if (!g) return fail(MOEINF_ERR_INVALID, "engine is NULL");
+  if (token_mask_dev && g->cfg.ep_size > 1)
+    return fail(MOEINF_ERR_UNSUPPORTED, "token masks are not supported under expert parallelism (ep_size %d)", g->cfg.ep_size);
+  return moe_forward(g, layer, x_dev, tokens, batch_rows, gate_w_dev, out_dev, stream, flags, token_mask_dev);
+}
+
+static int moe_forward(moeinf_engine* g, int layer, const void* x_dev, int tokens, int batch_rows, const void* gate_w_dev,
+                       void* out_dev, void* stream, uint32_t flags, const uint8_t* token_mask) {
   if (!g) return fail(MOEINF_ERR_INVALID, "engine is NULL");
   if (layer < 0 || layer >= g->L) return fail(MOEINF_ERR_INVALID, "layer %d out of range", layer);
   if (tokens <= 0 || tokens > g->cfg.max_tokens) return fail(MOEINF_ERR_INVALID, "tokens %d not in 1..max_tokens(%d)", tokens, g->cfg.max_tokens);
@@ -1633,6 +1647,7 @@ extern "C" int moeinf_moe_forward(moeinf_engine* g, int layer, const void* x_dev
   RouteArgs ra;
   make_route_args(g, x_dev, gate_w_dev, T, ra);
   if (g->route_v3) ra.e_bias = g->gate_bias[layer];
+  ra.token_mask = token_mask;  // read by route_core only (the next-layer lookahead route below inherits it)
   moeinf_engine::ProfRec pr;
   const bool prof = g->profiling && !route_only;
   if (prof) { for (int i = 0; i < 6; ++i) { pr.ev[i] = get_event(g); if (!pr.ev[i]) return fail(MOEINF_ERR_HIP, "hipEventCreate failed"); } HIPCHK(hipEventRecord(pr.ev[0], st)); }
@@ -1667,7 +1682,9 @@ extern "C" int moeinf_moe_forward(moeinf_engine* g, int layer, const void* x_dev
   static const int sr_multi_env = getenv("MOEINF_SELFROUTE_MULTI") ? atoi(getenv("MOEINF_SELFROUTE_MULTI")) : 8;
   static const int sr_multi_pairs = getenv("MOEINF_SELFROUTE_MULTI_PAIRS") ? atoi(getenv("MOEINF_SELFROUTE_MULTI_PAIRS")) : 24;
   const bool sr_multi = T >= 2 && T <= std::min(8, sr_multi_env) && T * K <= std::min(64, sr_multi_pairs) && sr_gated;
-  const bool selfroute = selfroute_env && !route_only && mp.fast && K <= 8 && E <= 64 && !g->ovr_out &&
+  // A token mask takes the generic router launches (route_core reads the mask): the self-routing forms (selfroute, multi,
+  // moe_front1, the Switch one-launch layer) and the fused combine assume every token keeps its K experts, so stage 2 always runs.
+  const bool selfroute = selfroute_env && !token_mask && !route_only && mp.fast && K <= 8 && E <= 64 && !g->ovr_out &&
                          ((T == 1 && (sr_gated || sr_switch)) || sr_multi);
   g->last_selfroute = selfroute;
   // (the whole DeepSeek layer as ONE persistent launch was built in round 5, measured slower — 1.09 vs 0.958 ms/token — and
@@ -1745,7 +1762,7 @@ extern "C" int moeinf_moe_forward(moeinf_engine* g, int layer, const void* x_dev
   // decode-sized Mixtral/DeepSeek forwards (every token keeps K experts, so stage 2 always runs): the combine
   // rides in the epilogue of FFN stage 2
   static const bool fuse_combine = getenv("MOEINF_FUSE_COMBINE") ? atoi(getenv("MOEINF_FUSE_COMBINE")) != 0 : true;
-  const bool can_fuse = fuse_combine && want_combine && T <= 16 &&
+  const bool can_fuse = fuse_combine && want_combine && T <= 16 && !token_mask &&
                         (g->cfg.router_kind == MOEINF_ROUTER_MIXTRAL || g->cfg.router_kind == MOEINF_ROUTER_DEEPSEEK ||
                          (selfroute && sr_switch));  // (Switch: only the batch-1 stage 2 knows its combine)
   bool fused = false;

@@ -837,6 +837,8 @@ template <bool COHL = false>  // COHL: the logits were written by other workgrou
 __device__ __forceinline__ void route_core(const RouteArgs& a, const int t, const int lane, Routed& o) {
   const int E = a.E, K = a.K;
   const float* lg = a.logits + (size_t)t * E;
+  // the token's mask byte, issued with the logits loads (no mask: a kernel-argument null check, one uniform branch)
+  const bool masked = a.token_mask && a.token_mask[t] == 0;
   float l[4], p[4];
   float m = -INFINITY;
 #pragma unroll
@@ -1019,6 +1021,12 @@ __device__ __forceinline__ void route_core(const RouteArgs& a, const int t, cons
     w[0] = val[0] / den; w[1] = val[1] / den;
     w[0] = round_model(xdt, w[0]); w[1] = round_model(xdt, w[1]);
     valid[0] = (w[0] != 0.f); valid[1] = (w[1] != 0.f);  // router_mask = combining_weights.bool()
+  }
+  // a masked token: every pair dropped by the router (id -1, weight 0), so no index counts it (Switch capacity included)
+  // and its output is the family's no-pair rule.  val0 stays: Switch's router_prob * x, as for a capacity-dropped token.
+  if (masked) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sel[k] = -1; w[k] = 0.f; valid[k] = 0; }
   }
 
 #pragma unroll

@@ -247,6 +247,7 @@ struct RouteArgs {
   int v3;               // kind DEEPSEEK only: 1 = DeepSeek-V3's gate (sigmoid scores, e_score_correction_bias, top-2-sum groups; modeling_deepseek_v3 MoEGate)
   const float* e_bias;  // ... its e_score_correction_bias [E] (fp32, device), or nullptr = zeros
   int no_renorm;        // kind MIXTRAL only: 1 = the top-k probabilities are NOT renormalised (Grok / Arctic, grok.py:38-45)
+  const uint8_t* token_mask;  // [T] device bytes, 0 = masked token (every pair dropped, no slot), or nullptr = all tokens real
 };
 hipError_t launch_gate_logits(const RouteArgs& a, hipStream_t st);
 hipError_t launch_route_topk(const RouteArgs& a, hipStream_t st);

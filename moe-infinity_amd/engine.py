@@ -77,6 +77,7 @@ class MoEEngine:
         self.device = torch.device("cuda", cfg.device_id)
         self._H, self._gate_shape = cfg.hidden, torch.Size((cfg.num_experts, cfg.hidden))
         self._moe_forward = self.lib.moeinf_moe_forward
+        self._moe_forward_masked = self.lib.moeinf_moe_forward_masked
         self._last_T = 0
         self._stores = set()  # OffloadStore objects experts were registered from (kept alive until close())
 
@@ -153,8 +154,11 @@ class MoEEngine:
             raise ValueError(f"{what} must be contiguous")
 
     def forward(self, layer: int, x: torch.Tensor, gate_w: torch.Tensor, batch_rows: int = 1,
-                out: Optional[torch.Tensor] = None, flags: int = FWD_DEFAULT) -> Optional[torch.Tensor]:
-        """One MoE layer: x [..., H] -> out [..., H] (same shape), enqueued on the current stream."""
+                out: Optional[torch.Tensor] = None, flags: int = FWD_DEFAULT,
+                token_mask: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """One MoE layer: x [..., H] -> out [..., H] (same shape), enqueued on the current stream.
+        token_mask: None, or bool / uint8 [T] or [B, S] on the engine's device, non-zero = real token.  A masked token takes
+        no expert; its row is the family's no-pair output (moeinf_moe_forward_masked, include/moeinf.h)."""
         # One comparison per tensor on the hot path; _check_dev (which names what is wrong) runs only when it fails.  The host
         # side of a sync-free forward is 15-20 us, the same order as a whole Switch-base-8 or DeepSeek-V2-Lite layer on the GPU.
         shape = x.shape
@@ -172,14 +176,34 @@ class MoEEngine:
                 out = torch.empty_like(x2)
         elif out.device != dev or out.dtype is not dt or not out.is_contiguous():
             self._check_dev(out, dt, "out")
-        rc = self._moe_forward(self._h, layer, x2.data_ptr(), T, batch_rows, gate_w.data_ptr(),
-                               out.data_ptr() if out is not None else None, _current_stream_handle(dev), flags)
+        if token_mask is None:
+            rc = self._moe_forward(self._h, layer, x2.data_ptr(), T, batch_rows, gate_w.data_ptr(),
+                                   out.data_ptr() if out is not None else None, _current_stream_handle(dev), flags)
+        else:
+            m = self._token_mask_bytes(token_mask, T)
+            rc = self._moe_forward_masked(self._h, layer, x2.data_ptr(), T, batch_rows, gate_w.data_ptr(),
+                                          out.data_ptr() if out is not None else None, _current_stream_handle(dev), flags,
+                                          m.data_ptr())
+            self._token_mask = m  # the kernels read it on the stream: keep it alive until the next forward
         if rc != 0:
             check(rc)
         self._last_T = T
         if out is None:
             return None
         return out if out.shape == shape else out.reshape(shape)
+
+    def _token_mask_bytes(self, token_mask: torch.Tensor, T: int) -> torch.Tensor:
+        """bool / uint8 [T] or [B, S] (B * S == T) on the engine's device -> contiguous uint8 [T]"""
+        if not token_mask.is_cuda or token_mask.device != self.device:
+            raise ValueError(f"token_mask must live on cuda:{self.cfg.device_id}")
+        if token_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"token_mask must be torch.bool or torch.uint8, got {token_mask.dtype}")
+        if token_mask.dim() not in (1, 2) or token_mask.numel() != T:
+            raise ValueError(f"token_mask must be [T] or [B, S] with {T} elements, got {tuple(token_mask.shape)}")
+        m = token_mask.reshape(T)
+        if m.dtype == torch.bool:
+            m = m.contiguous().view(torch.uint8)
+        return m.contiguous()
 
     def dispatch_mask(self, layer: int, x2: torch.Tensor, router_mask: torch.Tensor, experts: Optional[Sequence[int]] = None):
         """Grouped expert FFN for a dense router_mask[T,E] (the reference's dispatch_local contract).
