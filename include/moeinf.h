@@ -139,20 +139,30 @@ typedef struct moeinf_stats {
 const char* moeinf_last_error(void);
 int moeinf_abi_version(void);
 
-/* ---- introspection for tests (no reference counterpart, no GPU needed): which form of the register-ring GEMM
- * (csrc/ffn_ring2_kernel.h: ffn_gemm_ring2) the launcher picks for an FFN stage.  dtype: MOEINF_DTYPE_*; nmat: 2 = gated stage,
- * 1 = plain; K / K_sh: reduction length of the routed / shared experts (0: no shared expert); R: output rows; active: experts
- * with rows (the grid's upper bound); max_rows: rows of the busiest expert as the engine passes it (1.5 x the mean + 1 on the
- * sync-free path); num_cus: compute units.  out[0] = token groups of 16 per pass (0: another kernel runs), out[1] = 1 when the
- * last round of workgroups is split into half workgroups, out[2] = row blocks per expert, out[3] = first split unit,
- * out[4] = workgroups launched.  Environment knobs are honoured as in the launcher. */
 /* the row estimate moeinf_moe_forward passes to the FFN launchers when every expert of the layer is resident (sync-free path) */
 int moeinf_rows_estimate(int tokens, int top_k, int num_experts);
+/* ---- introspection for tests (no reference counterpart, no GPU needed): which kernel, and which form of it, the launcher picks
+ * for an FFN stage.  One function decides for every dtype (csrc/kernels.h ffn_form); these exports report
+ * what it gives, with the environment knobs as they are at the call (the launcher reads them once per process).
+ * dtype: MOEINF_DTYPE_*, MOEINF_DTYPE_F8E4M3 = an fp8 slot (bf16 activations, fp8 routed weights); epi: the stage's epilogue
+ * (csrc/kernels.h EPI_*: 0 none, 1 bias, 2 relu, 3 bias + relu, 4 gated SiLU, 5 gated GELU; 4 and 5 are the gated stage);
+ * K / K_sh: reduction length of the routed / shared experts (K_sh = 0: no shared expert rides in the launch); R: output rows
+ * (the larger of the routed and the shared expert's); active: experts with rows (the grid's upper bound); max_rows: rows of the
+ * busiest expert as the engine passes it (1.5 x the mean + 1 on the sync-free path); num_cus: compute units; flags: bit 0
+ * ld_out % 8 != 0, bit 1 rows_bound * ld_in does not fit in 32 bits, bit 2 the stage fuses the combine.
+ * out[0]: -1 = no kernel (an fp8 stage the kernels do not take), 0 = the row kernel, 1 = ffn_gemm_hyb, 2 = ffn_gemm_lds,
+ * 3 = ffn_gemm_ring2, 4 = ffn_gemm (register GEMM), 5 = ffn_gemm_big; out[1]: waves per workgroup; out[2]: unroll (row kernel);
+ * out[3]: token groups of 16 per pass (row kernel, register GEMM); out[4]: row groups per wave (hyb); out[5]: k-tiles per stage
+ * (hyb); out[6]: full-line activation staging (hyb, lds); out[7]: row groups per workgroup (lds); out[8]: passes per launch (big);
+ * out[9..13]: ring2's form (as out[0..4] of moeinf_ffn_ring2_form). */
+int moeinf_ffn_form(int dtype, int epi, int K, int K_sh, int R, int active, int max_rows, int num_cus, int flags, int32_t* out14);
+/* The ring2 part of moeinf_ffn_form for a gated-SiLU (nmat = 2) or plain no-epilogue (nmat = 1) stage of dtype (arguments as
+ * above): out[0] = token groups of 16 per pass (0: another kernel runs), out[1] = 1 when the last round of workgroups is split into
+ * half workgroups, out[2] = row blocks per expert, out[3] = first split unit, out[4] = workgroups launched. */
 int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out5);
-/* Which grouped GEMM an FFN stage of an fp8-slot engine (moeinf_create_ex) takes (csrc/kernels.h f8_gemm_form; arguments as
- * above, K_sh = 0 when no shared expert rides in the launch).  out[0]: 0 = the row kernel, 1 = ffn_gemm_hyb, 2 = ffn_gemm_lds,
- * 3 = ffn_gemm_ring2 (their fp8-weight forms); out[1]: waves per workgroup (hyb, lds) or token groups per pass (ring2);
- * out[2..5]: ring2's split tail, row blocks per expert, first split unit, workgroups (as out[1..4] of moeinf_ffn_ring2_form). */
+/* moeinf_ffn_form for a stage of an fp8-slot engine (moeinf_create_ex), as out[0] = 0 the row kernel, 1 = ffn_gemm_hyb,
+ * 2 = ffn_gemm_lds, 3 = ffn_gemm_ring2 (their fp8-weight forms); out[1]: waves per workgroup (hyb, lds) or token groups per pass
+ * (ring2); out[2..5]: ring2's split tail, row blocks per expert, first split unit, workgroups (as out[1..4] of moeinf_ffn_ring2_form). */
 int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out6);
 /* The fence ring (csrc/engine_internal.h): sync-free forwards record a fence event only every MOEINF_FENCE_EVERY-th time; a copy
  * that recycles a slot waits for the OLDEST recorded fence that covers the slot's last reader.  moeinf_fence_ring: entries in the

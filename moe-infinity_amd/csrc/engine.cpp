@@ -71,19 +71,44 @@ extern "C" int moeinf_fence_cover_pos(const uint64_t* fence_seq, uint64_t record
   return fence_seq ? fence_cover_pos(fence_seq, recorded, forward) : -1;
 }
 
+// the form ffn_form gives a stage of these arguments (include/moeinf.h); the knobs as the environment holds them NOW (the launch path
+// reads them once per process)
+static moeinf::FfnForm ffn_form_of(int dtype, int epi, int K, int K_sh, int R, int active, int max_rows, int num_cus, int flags) {
+  moeinf::FfnStage s;
+  memset(&s, 0, sizeof s);
+  const bool f8w = dtype == MOEINF_DTYPE_F8E4M3;
+  s.dtype = f8w ? moeinf::DT_BF16 : dtype; s.wdtype = f8w ? moeinf::DT_F8 : dtype;
+  s.epi = epi; s.K = K; s.R = R; s.K_sh = K_sh; s.R_sh = K_sh > 0 ? R : 0;
+  s.ld_in = 1; s.ld_out = (flags & 1) ? 4 : 8; s.rows_bound = (flags & 2) ? int64_t(1) << 32 : 0; s.fuse_combine = (flags & 4) ? 1 : 0;
+  return moeinf::ffn_form(moeinf::ffn_shape(s), active, max_rows, num_cus, moeinf::FfnKnobs::from_env());
+}
+
+extern "C" int moeinf_ffn_form(int dtype, int epi, int K, int K_sh, int R, int active, int max_rows, int num_cus, int flags, int32_t* out14) {
+  if (!out14 || epi < moeinf::EPI_NONE || epi > moeinf::EPI_GATED_GELU || K <= 0 || K_sh < 0 || R <= 0 || active <= 0)
+    return fail(MOEINF_ERR_INVALID, "moeinf_ffn_form: bad arguments");
+  const moeinf::FfnForm f = ffn_form_of(dtype, epi, K, K_sh, R, active, max_rows, num_cus, flags);
+  const int32_t v[14] = {f.kernel, f.waves, f.unroll, f.nt, f.rw, f.kk, f.xl, f.rgb, f.passes,
+                         f.ring.ntb, f.ring.tail, f.ring.nblk, f.ring.split, f.ring.blocks};
+  memcpy(out14, v, sizeof v);
+  return MOEINF_OK;
+}
+
 extern "C" int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out5) {
   if (!out5 || (nmat != 1 && nmat != 2) || K <= 0 || R <= 0 || active <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_ffn_ring2_form: bad arguments");
   const bool two_bytes = dtype == MOEINF_DTYPE_BF16 || dtype == MOEINF_DTYPE_F16;
-  const moeinf::Ring2Form f = moeinf::ring2_form(two_bytes ? 2 : 4, dtype == MOEINF_DTYPE_F16, nmat, K, K_sh, (R + 15) / 16, active, max_rows, num_cus,
-                                                 moeinf::Ring2Knobs::from_env());
-  out5[0] = f.ntb; out5[1] = f.tail; out5[2] = f.nblk; out5[3] = f.split; out5[4] = f.blocks;
+  const moeinf::FfnForm f = ffn_form_of(two_bytes ? dtype : MOEINF_DTYPE_F32, nmat == 2 ? moeinf::EPI_GATED_SILU : moeinf::EPI_NONE, K, K_sh, R,
+                                        active, max_rows, num_cus, 0);
+  out5[0] = f.ring.ntb; out5[1] = f.ring.tail; out5[2] = f.ring.nblk; out5[3] = f.ring.split; out5[4] = f.ring.blocks;
   return MOEINF_OK;
 }
 
 extern "C" int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out6) {
   if (!out6 || (nmat != 1 && nmat != 2) || K <= 0 || K_sh < 0 || R <= 0 || active <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_ffn_f8_gemm_form: bad arguments");
-  const moeinf::F8GemmForm f = moeinf::f8_gemm_form(nmat, K, K_sh, (R + 15) / 16, active, max_rows, num_cus, moeinf::F8GemmKnobs());
-  out6[0] = f.kernel; out6[1] = f.width;
+  const moeinf::FfnForm f = ffn_form_of(MOEINF_DTYPE_F8E4M3, nmat == 2 ? moeinf::EPI_GATED_SILU : moeinf::EPI_NONE, K, K_sh, R, active,
+                                        max_rows, num_cus, 0);
+  const bool gemm = f.kernel == moeinf::FFN_HYB || f.kernel == moeinf::FFN_LDS || f.kernel == moeinf::FFN_RING2;
+  out6[0] = gemm ? f.kernel : moeinf::FFN_ROWS;
+  out6[1] = f.kernel == moeinf::FFN_RING2 ? f.ring.ntb : (gemm ? f.waves : 0);
   out6[2] = f.ring.tail; out6[3] = f.ring.nblk; out6[4] = f.ring.split; out6[5] = f.ring.blocks;
   return MOEINF_OK;
 }
@@ -246,7 +271,7 @@ static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine**
 extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, false, out); }
 
 // fp8 slots: what the fp8-weight kernels cover (kernels.hip / layer_fused.hip: the row-dot forms of the gated families); every
-// other configuration is refused here, so the kernels that have no fp8 form (grouped GEMMs are declined by their launchers; the
+// other configuration is refused here, so the kernels that have no fp8 form (ffn_form picks no such grouped GEMM; the
 // Switch one-launch layer, the expert-parallel owner kernels) are never reached
 static int check_fp8_slots(const moeinf_config* c) {
   if (c->dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need fp8 experts (dtype %d, not %d)", MOEINF_DTYPE_F8E4M3, c->dtype);
@@ -300,6 +325,7 @@ static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine**
   DeviceScope on_dev_(cfg->device_id); HIPCHK(on_dev_.err);
   moeinf_engine* g = new moeinf_engine();
   g->cfg = *cfg;
+  if (hipDeviceGetAttribute(&g->num_cus, hipDeviceAttributeMultiprocessorCount, cfg->device_id) != hipSuccess || g->num_cus <= 0) g->num_cus = 256;
   // Grok / Arctic (moe_infinity/models/grok.py:38-45): Mixtral's router without the renormalisation.  Everything else about the
   // kind — bf16 gate logits, selection, dispatch, combine, which kernels run — is Mixtral's: the engine keeps ONE kind for it
   // and a flag for the weights.
@@ -1396,10 +1422,10 @@ static int run_experts(moeinf_engine* g, int layer, const void* x_in, hipStream_
     // then pick the same kernel form unless the routing is skewed beyond 1.5 x the mean
     int max_rows = rows_hint;
     for (int i = a; i < b; ++i) max_rows = std::max(max_rows, (int)g->h_mirror[1 + active[i]]);
-    HIPCHK(launch_ffn_stage(s1, b - a, max_rows, st));
+    HIPCHK(launch_ffn_stage(s1, b - a, max_rows, g->num_cus, st));
     if (ev_mid && b == na) HIPCHK(hipEventRecord(ev_mid, st));
     CHK(wait_late(g, layer, st, late));  // stage 2 reads the down projections: wait for the rest of each transfer
-    HIPCHK(launch_ffn_stage(s2, b - a, max_rows, st));
+    HIPCHK(launch_ffn_stage(s2, b - a, max_rows, g->num_cus, st));
     if (la_now && !la_early) CHK(lookahead_issue(g, layer));
     a = b;
     if (a < na) CHK(end_forward(g, st, true));
@@ -1449,7 +1475,6 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
       sy.ctr = g->d_layer_ctr; sy.launch = g->layer1_launches + 1; sy.timeout_ticks = g->layer1_timeout_ticks; sy.err = g->d_miss; sy.err_host = g->h_miss;
       static const int l1_sleep = getenv("MOEINF_LAYER1_SLEEP") ? std::max(1, atoi(getenv("MOEINF_LAYER1_SLEEP"))) : 2;
       sy.sleep = l1_sleep; sy.scalar_poll = g->layer1_scalar_poll ? 1 : 0;
-      if (!g->num_cus) (void)hipDeviceGetAttribute(&g->num_cus, hipDeviceAttributeMultiprocessorCount, g->cfg.device_id);  // per engine: engines of one process may sit on different devices
       if (g->layer1_switch_wgs_per_cu < 0) g->layer1_switch_wgs_per_cu = layer1_switch_wgs_per_cu(sr->ra->x_dtype, sr->ra->gate_dtype);  // asked once: registers + LDS of the instantiation
       const int ncu = g->num_cus;
       if (getenv("MOEINF_LAYER1_TRACE")) {
@@ -1497,14 +1522,14 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
     }
     else {
       if (kt1) arm_kernel_timer(pr->ev[2], pr->ev[3]);
-      const hipError_t le = launch_ffn_stage(s1, max_active, exp_rows, st);
+      const hipError_t le = launch_ffn_stage(s1, max_active, exp_rows, g->num_cus, st);
       disarm_kernel_timer();
       HIPCHK(le);
     }
     if (prof && !kt1) HIPCHK(hipEventRecord(pr->ev[3], st));
     {
       if (kt2 && (pr->k2 = get_event(g))) arm_kernel_timer(pr->k2, pr->ev[4]);
-      const hipError_t le = (sr && fuse && T == 1) ? launch_ffn2_decode1(s2, st) : launch_ffn_stage(s2, max_active, exp_rows, st);
+      const hipError_t le = (sr && fuse && T == 1) ? launch_ffn2_decode1(s2, st) : launch_ffn_stage(s2, max_active, exp_rows, g->num_cus, st);
       disarm_kernel_timer();
       HIPCHK(le);
     }

@@ -289,8 +289,8 @@ static int ep_combine_impl(moeinf_engine* g, const void* x_dev, const void* ret_
     s1.in = x_dev;
     fill_stage(g, g->last_layer, 2, s2);
     s1.n_active_host = 1; s2.n_active_host = 1;
-    HIPCHK(launch_ffn_stage(s1, 1, T, st));
-    HIPCHK(launch_ffn_stage(s2, 1, T, st));
+    HIPCHK(launch_ffn_stage(s1, 1, T, g->num_cus, st));
+    HIPCHK(launch_ffn_stage(s2, 1, T, g->num_cus, st));
   }
   CombineArgs ca;
   memset(&ca, 0, sizeof ca);

@@ -559,21 +559,17 @@ __global__ __launch_bounds__(512) void ffn_gemm_big_kernel(FfnStage s, int nx, i
   }
 }
 
-// max_rows: (an estimate of) the rows of the busiest expert; the kernel's pass loop covers more
-bool launch_ffn_gemm_big(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st) {
-  if (s.wdtype == DT_F8) return false;  // fp8 slots: not built here (the row kernel's fp8 form, kernels.hip)
-  if (s.dtype == DT_F32 || (s.K % 64) != 0 || (s.K_sh % 64) != 0 || (s.ld_out % 8) != 0) return false;  // 16-byte row stores
-  if ((nmat == 2) != (s.epi == EPI_GATED_SILU)) return false;
+// f.passes: passes over the tokens one launch holds, from (an estimate of) the rows of the busiest expert; the kernel's pass loop
+// covers more
+void launch_ffn_gemm_big(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st) {
+  const int nmat = f.nmat, num_cus = f.num_cus;
   const int rmax = s.R > s.R_sh ? s.R : s.R_sh;
-  const int passes = max_rows <= 256 ? 1 : (max_rows + 255) / 256;
-  const int nx = (rmax + 255 / nmat) / (256 / nmat), ny = (int)grid.y, nz = passes > 8 ? 8 : passes;
+  const int nx = (rmax + 255 / nmat) / (256 / nmat), ny = (int)grid.y, nz = f.passes;
   static const int chunk_env = env_int("MOEINF_GEMM_BIG_CHUNK", 4);
   const int chunk = chunk_env < 1 ? 1 : chunk_env;
   // short last passes of the plain stage with a long reduction run from the END of the grid when the full passes are two or more
   // exact rounds (kernel: SHORT region).  MOEINF_GEMM_BIG_MOVE: 0 = never (the round-5 form), 1 = by that rule (default), 2 = always
   static const int move_env = env_int("MOEINF_GEMM_BIG_MOVE", 1);
-  static int num_cus = 0;
-  if (!num_cus) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || num_cus <= 0) num_cus = 256; }
   const int move_short = (nmat == 1 && s.K >= 4096) ? std::max(0, std::min(2, move_env)) : 0;
   const int per8 = chunk * (((nx * ny + chunk - 1) / chunk + 7) / 8) * 8;
   const dim3 g((unsigned)(per8 * (nz + (move_short ? 1 : 0))));
@@ -585,7 +581,7 @@ bool launch_ffn_gemm_big(const FfnStage& s, int nmat, dim3 grid, int max_rows, h
   if (s.dtype == DT_F16) {  // fp16 experts: the default schedule only (three-deep weight ring, ping-pong)
     if (nmat == 2) KL((ffn_gemm_big_kernel<half_t, 2, true, 2>), g, dim3(512), 0, st, s, nx, ny, nz, xcd_map, tail_max, chunk, move_short, num_cus);
     else KL((ffn_gemm_big_kernel<half_t, 1, true, 2>), g, dim3(512), 0, st, s, nx, ny, nz, xcd_map, tail_max, chunk, move_short, num_cus);
-    return true;
+    return;
   }
   if (ring3) {
     if (mode == 3) { if (nmat == 2) BIGGO(2, true, 3); else BIGGO(1, true, 3); }
@@ -595,7 +591,6 @@ bool launch_ffn_gemm_big(const FfnStage& s, int nmat, dim3 grid, int max_rows, h
     if (nmat == 2) BIGGO(2, false, 1); else BIGGO(1, false, 1);
   }
 #undef BIGGO
-  return true;
 }
 
 }  // namespace moeinf

@@ -1,4 +1,4 @@
-// ffn_gemm_f16.hip — fp16 entry points (the reference's expert dtype id 2, core/parallel/expert_module.h:20-23) of the
+// ffn_gemm_f16.hip — fp16 entry point (the reference's expert dtype id 2, core/parallel/expert_module.h:20-23) of the
 // grouped-GEMM kernels for experts with many rows: the hybrid (17 .. 64 / 128 rows per expert) and the LDS-staged kernel
 // (.. 256 rows) on the f16 matrix instruction, so that the short-reduction families (DeepSeek-V2-Lite, NLLB's first stage)
 // run fp16 at every size without falling back to the decode kernel looping over token tiles (round 5; until then only the
@@ -7,7 +7,8 @@
 
 namespace moeinf {
 
-template bool launch_ffn_gemm<half_t, 1>(const FfnStage&, dim3, int, hipStream_t);
-template bool launch_ffn_gemm<half_t, 2>(const FfnStage&, dim3, int, hipStream_t);
+void launch_ffn_gemm_f16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st) {
+  if (f.nmat == 1) launch_ffn_gemm_t<half_t, 1>(s, grid, f, st); else launch_ffn_gemm_t<half_t, 2>(s, grid, f, st);
+}
 
 }  // namespace moeinf

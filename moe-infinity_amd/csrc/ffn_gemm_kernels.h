@@ -1,8 +1,7 @@
 // ffn_gemm_kernels.h — the grouped-GEMM forms of the expert FFN stage for experts with MANY rows (prefill, large batches):
 // ffn_gemm (register-tiled), ffn_gemm_lds (both operands through LDS), ffn_gemm_hyb (activations through LDS, weights
 // straight to registers); ffn_gemm_ring2 (register ring of weight tiles, software-pipelined; long reductions) lives in
-// ffn_gemm_ring2.hip.  Selected by launch_ffn_gemm, which
-// launch_ffn_stage (kernels.hip) calls for more than 16 rows per expert.
+// ffn_gemm_ring2.hip.  Which one runs, and in which form: ffn_form (kernels.h).
 // Included by ffn_gemm.hip (bf16 and fp32 instantiations) and ffn_gemm_f16.hip (fp16, round 5): two translation units, so that
 // the dtypes compile in parallel.
 #pragma once
@@ -11,9 +10,6 @@
 #include <type_traits>
 
 namespace moeinf {
-
-// ffn_gemm_ring2.hip: the register-ring kernel, launched when ring2_form (kernels.h) picks one of its forms; false: not handled
-bool launch_ffn_gemm_ring2_bf16(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);
 
 // fp8-slot bodies (T = f8w_t): ffn_gemm_f8_kernels.h
 template <int NMAT, int RGB, int NWV, bool XL> __device__ __forceinline__ void ffn_gemm_lds_kernel_f8w(const FfnStage& s);
@@ -525,92 +521,31 @@ __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
   }
 }
 
+// the hybrid, LDS-staged or register GEMM in the form ffn_form chose; instantiated by ffn_gemm.hip (bf16, fp32), ffn_gemm_f16.hip
+// and ffn_gemm_f8.hip (fp8 slots: no register GEMM)
 template <typename T, int NMAT>
-bool launch_ffn_gemm(const FfnStage& s, dim3 grid, int max_rows, hipStream_t st) {
-  if (s.wdtype == DT_F8) return false;  // fp8 slots: not built here (the row kernel's fp8 form, kernels.hip)
-  if (NMAT == 2 && s.epi != EPI_GATED_SILU) return false;  // (the gelu gate: the row kernel, kernels.hip)
-  static const int use_gemm = env_int("MOEINF_FFN_GEMM", 2);
-  static const int force_nt = env_int("MOEINF_FFN_GEMM_NT", 0);
-  // long prefills: the 256 x 256 / 32x32x16-MFMA kernel (ffn_gemm_big.hip).  Measured (profiles/r03_ffn_sweep_prefill_big_*.txt):
-  // it beats ffn_gemm_lds from 257 rows per expert on (Mixtral down projection at 2048 tokens 846 -> 730 us, DeepSeek-V2-Lite
-  // at 4096 tokens 2.54 -> 1.96 ms per layer).  The register-ring kernel (gated stage, K >= 4096) held out to ~640 rows
-  // against the first ping-pong version; with the short-last-pass variant the big kernel wins from 257 rows on (Mixtral
-  // gate/up: 768 tokens 503 vs 535 us, 1024 tokens 647 vs 748, 1536 tokens 845 vs 1 031, 2048 tokens 1 010 vs 1 250), so
-  // both stages switch at the same row count now; below it (512 tokens: 436 vs 450 gate/up but 324 vs 265 down) ring / lds stay
-  static const int big_env = env_int("MOEINF_GEMM_BIG", 1);
-  static const int big_rows = env_int("MOEINF_GEMM_BIG_ROWS", 256);
-  const int ept = sizeof(T) == 2 ? 32 : 16;
-  const bool k_ok = (s.K % ept) == 0 && (s.K_sh % ept) == 0;
-  // 17-64 rows per expert (e.g. NLLB's 128 experts at a 2048-token batch): too many for the decode kernel, too few to
-  // amortise staging the weights in LDS -> the hybrid kernel (measured -15 % on that shape, sweep in profiles/)
-  // hybrid kernel (weights -> registers) up to 64 rows per expert; up to 128 when few experts are active (<= 16: big
-  // matrices, few workgroups — Mixtral at 192 / 256 / 320 tokens: down projection 213 -> 174, 227 -> 208, 232 -> 226 us; with
-  // NLLB's 128 experts at 4096 tokens the same switch costs +11 %)
-  static const Ring2Knobs knobs0 = Ring2Knobs::from_env();
-  const int hyb_rows = hyb_rows_for((int)grid.y, knobs0);
-  if constexpr (sizeof(T) == 2) {
-    // long reductions (K >= 4096: Mixtral's two stages, NLLB's second), 17 (plain) / hyb_rows+1 (gated) .. 340 rows per expert:
-    // the software-pipelined register ring.  Measured against what ran there before (profiles/r04_ffn_sweep_ring2_*.txt,
-    // Mixtral-8x7B, us per layer, gate-up / down):
-    //   tokens   96       224       336       384       512       640       768       896
-    //   before   320/162  337/196   365/233   404/252   441/261   494/274   492/342   510/347   (hybrid | ring + lds | big)
-    //   ring2    (hyb)/147 (hyb)/157 (hyb)/173 347/178   374/202   401/233   438/256   487/287
-    // gated stage below 129 rows: the hybrid kernel is 1-2 % ahead and stays.  Above ~256 rows per expert (the row estimate of
-    // the sync-free path is 1.5 x the mean + 1 = 337 at 896 tokens, 385 at 1 024) a second pass over the weights begins and the
-    // big-tile kernel takes over.  An expert with more rows than a pass holds takes another pass; correctness never depends on
-    // the estimate.
-    if constexpr (std::is_same<T, uint16_t>::value) {
-      if (use_gemm == 2 && launch_ffn_gemm_ring2_bf16(s, NMAT, grid, max_rows, st)) return true;
-    }
-  }
-  if (use_gemm == 2 && big_env && sizeof(T) == 2 && max_rows > big_rows && launch_ffn_gemm_big(s, NMAT, grid, max_rows, st)) return true;
-  if ((use_gemm == 3 || (use_gemm == 2 && max_rows <= hyb_rows)) && k_ok) {  // weights -> registers, activations -> LDS
-    static const int kk = env_int("MOEINF_GEMM_HYB_KK", 4);
-    static const int hxl_env = env_int("MOEINF_GEMM_XL", 1);
-    const bool hxl = hxl_env && (s.K % (2 * ept)) == 0 && (s.K_sh % (2 * ept)) == 0;
-#define HYB(NM, RWV, KKV, XLV) KL((ffn_gemm_hyb_kernel<T, NM, RWV, KKV, XLV>), dim3((grid.x + 4 * RWV - 1) / (4 * RWV), grid.y), dim3(256), 0, st, s)
-    if constexpr (NMAT == 2) {
-      if (kk == 2) { if (hxl) HYB(2, 1, 2, true); else HYB(2, 1, 2, false); }
-      else { if (hxl) HYB(2, 1, 4, true); else HYB(2, 1, 4, false); }
-    } else {
-      if (kk == 2) { if (hxl) HYB(1, 2, 2, true); else HYB(1, 2, 2, false); }
-      else { if (hxl) HYB(1, 2, 4, true); else HYB(1, 2, 4, false); }
-    }
+void launch_ffn_gemm_t(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st) {
+  if (f.kernel == FFN_HYB) {  // weights -> registers, activations -> LDS
+#define HYB(RWV, KKV, XLV) KL((ffn_gemm_hyb_kernel<T, NMAT, RWV, KKV, XLV>), dim3((grid.x + 4 * RWV - 1) / (4 * RWV), grid.y), dim3(256), 0, st, s)
+    constexpr int RW = NMAT == 2 ? 1 : 2;
+    if (f.kk == 2) { if (f.xl) HYB(RW, 2, true); else HYB(RW, 2, false); }
+    else { if (f.xl) HYB(RW, 4, true); else HYB(RW, 4, false); }
 #undef HYB
-  } else if (use_gemm == 2 && k_ok) {  // LDS-staged grouped GEMM
-    static const int rgb_plain = env_int("MOEINF_FFN_GEMM_RGB", 0);
-    static const int wide_env = env_int("MOEINF_GEMM_WIDE", -1);
-    const bool wide = wide_env >= 0 ? wide_env != 0 : max_rows > 128;  // 8 waves: 256 tokens per pass over the weights
-    static const int xl_env = env_int("MOEINF_GEMM_XL", 1);
-    const bool xl = xl_env && (s.K % (2 * ept)) == 0 && (s.K_sh % (2 * ept)) == 0;  // full-line activation staging
-    auto go = [&](auto kern, int rgb, int nwv) {
-      KL(kern, dim3((grid.x + rgb - 1) / rgb, grid.y), dim3(nwv * 64), 0, st, s);
-    };
-#define GO(NM, RG, NW) do { if (xl) go(ffn_gemm_lds_kernel<T, NM, RG, NW, true>, RG, NW); else go(ffn_gemm_lds_kernel<T, NM, RG, NW, false>, RG, NW); } while (0)
-    if constexpr (NMAT == 2) {
-      static const int rgb_gated = env_int("MOEINF_FFN_GEMM_RGB2", 4);
-      if (rgb_gated == 8) { if (wide) GO(2, 8, 8); else GO(2, 8, 4); }
-      else { if (wide) GO(2, 4, 8); else GO(2, 4, 4); }
-    } else {
-      // 128-row blocks need >= 2 blocks per CU to hide the DMA latency; fall back to 64-row blocks otherwise
-      const bool big = rgb_plain ? rgb_plain == 8 : (((grid.x + 7) / 8) * grid.y >= 512 && s.K >= 4096);
-      if (big) { if (wide) GO(1, 8, 8); else GO(1, 8, 4); }
-      else     { if (wide) GO(1, 4, 8); else GO(1, 4, 4); }
-    }
+  } else if (f.kernel == FFN_LDS) {  // LDS-staged grouped GEMM
+    auto go = [&](auto kern, int rgb, int nwv) { KL(kern, dim3((grid.x + rgb - 1) / rgb, grid.y), dim3(nwv * 64), 0, st, s); };
+#define GO(RG, NW) do { if (f.xl) go(ffn_gemm_lds_kernel<T, NMAT, RG, NW, true>, RG, NW); else go(ffn_gemm_lds_kernel<T, NMAT, RG, NW, false>, RG, NW); } while (0)
+    if (f.rgb == 8) { if (f.waves == 8) GO(8, 8); else GO(8, 4); }
+    else { if (f.waves == 8) GO(4, 8); else GO(4, 4); }
 #undef GO
-  } else if (use_gemm) {
-    const int nt = force_nt ? force_nt : 4;  // measured: (RG,NT)=(2,4)/(4,4) beats (1,8)/(2,8) at t_e ~128 (profiles/r01_ffn_sweep_prefill_gemm.txt)
+  } else if constexpr (!std::is_same<T, f8w_t>::value) {  // register GEMM
     if constexpr (NMAT == 2) {  // gated: 2 matrices -> (RG, NT) = (2,4) or (1,8)
-      if (nt <= 4) KL((ffn_gemm_kernel<T, 2, 2, 4, 4>), dim3((grid.x + 1) / 2, grid.y), dim3(256), 0, st, s);
+      if (f.nt <= 4) KL((ffn_gemm_kernel<T, 2, 2, 4, 4>), dim3((grid.x + 1) / 2, grid.y), dim3(256), 0, st, s);
       else KL((ffn_gemm_kernel<T, 2, 1, 8, 4>), grid, dim3(256), 0, st, s);
     } else {                    // plain: (4,4) or (2,8)
-      if (nt <= 4) KL((ffn_gemm_kernel<T, 1, 4, 4, 4>), dim3((grid.x + 3) / 4, grid.y), dim3(256), 0, st, s);
+      if (f.nt <= 4) KL((ffn_gemm_kernel<T, 1, 4, 4, 4>), dim3((grid.x + 3) / 4, grid.y), dim3(256), 0, st, s);
       else KL((ffn_gemm_kernel<T, 1, 2, 8, 4>), dim3((grid.x + 1) / 2, grid.y), dim3(256), 0, st, s);
     }
-  } else {
-    return false;
   }
-  return true;
 }
 
 }  // namespace moeinf

@@ -287,10 +287,6 @@ __global__ __launch_bounds__(512) void ffn_gemm_ring2_kernel(FfnStage s) {
 // launch the form ring2_form (kernels.h) chose: 128 / 192 / 256 tokens per pass; the gated stage with a split tail when the last
 // round of workgroups would fill at most half of the CUs (Mixtral's gate-up: 112 row blocks x 8 experts = 896 workgroups = 3.5
 // rounds on 256 CUs -> the last 128 units go out as 256 half workgroups of four working waves, 64 rows each)
-static int ring2_num_cus() {
-  static const int ncu = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
-  return ncu;
-}
 template <typename T, int NMAT>
 static void launch_ring2(const FfnStage& s0, dim3 grid, const Ring2Form& f, hipStream_t st) {
   const dim3 g2((unsigned)f.nblk, grid.y);

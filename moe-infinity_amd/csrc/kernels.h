@@ -119,34 +119,62 @@ struct FfnStage {
   int ring2_nblk;          // row blocks per expert (0: the plain 2-D grid)
   int ring2_split;
   // upper bound of the row index the stage reads from `in` (engine: max_tokens * (K + 1)); 0 = unknown.  ffn_gemm_ring2 keeps
-  // element offsets into `in` in 32 bits: its launchers decline a stage whose rows_bound * ld_in does not fit (round-4 advice)
+  // element offsets into `in` in 32 bits: ffn_form does not pick it for a stage whose rows_bound * ld_in does not fit (round-4 advice)
   int64_t rows_bound;
 };
 
-// ---- which form of ffn_gemm_ring2 a stage takes: pure host logic, shared by the launchers (ffn_gemm.hip) and the introspection
-// export moeinf_ffn_ring2_form (engine.cpp), which tests/test_kernel_selection_cpu.py pins against DESIGN.md section 4.3.
-// (Round 4: the launcher once asked for max_rows <= 192 where the sync-free path's estimate is 193 — the kernel silently never
-// ran and six experiments measured its predecessor.)
-struct Ring2Knobs {
-  int enable_bits = 3;   // MOEINF_GEMM_RING2: bit 0 gated stage, bit 1 plain stage
-  int min_k = 4096;      // MOEINF_RING_MIN_K
-  int max_rows = 340;    // MOEINF_RING2_MAX_ROWS: above, a second pass over the weights begins -> the big-tile kernel
-  int min_gated = 0;     // MOEINF_RING2_MIN_ROWS_GATED (0: where the hybrid kernel stops)
-  int min_plain = 16;    // MOEINF_RING2_MIN_ROWS_PLAIN
-  int tail = 1;          // MOEINF_RING2_TAIL: split a half-empty last round of the gated stage into half workgroups
-  int hyb_rows = 0;      // MOEINF_GEMM_HYB_ROWS (0: 128 with <= 16 active experts, else 64)
-  static int env_or(const char* n, int d) { const char* v = getenv(n); return v && *v ? atoi(v) : d; }
-  static Ring2Knobs from_env() {
-    Ring2Knobs k;
-    k.enable_bits = env_or("MOEINF_GEMM_RING2", k.enable_bits); k.min_k = env_or("MOEINF_RING_MIN_K", k.min_k);
-    k.max_rows = env_or("MOEINF_RING2_MAX_ROWS", k.max_rows); k.min_gated = env_or("MOEINF_RING2_MIN_ROWS_GATED", k.min_gated);
-    k.min_plain = env_or("MOEINF_RING2_MIN_ROWS_PLAIN", k.min_plain); k.tail = env_or("MOEINF_RING2_TAIL", k.tail);
-    k.hyb_rows = env_or("MOEINF_GEMM_HYB_ROWS", k.hyb_rows);
+// ---- which kernel, and which form of it, an FFN stage takes: pure host logic in plain C++ (engine.cpp includes this header).  ONE
+// function, ffn_form, decides for every dtype; launch_ffn_stage (kernels.hip) and the introspection exports (moeinf_ffn_form,
+// moeinf_ffn_ring2_form, moeinf_ffn_f8_gemm_form; engine.cpp) call it, and tests/test_ffn_form_cpu.py,
+// tests/test_kernel_selection_cpu.py and tests/test_fp8_gemm_selection_cpu.py pin it against DESIGN.md section 4.3.  (Round 4: the
+// launcher once asked for max_rows <= 192 where the sync-free path's estimate is 193 — the kernel silently never ran and six
+// experiments measured its predecessor.)
+
+// every environment knob that steers the choice (sweeps only): the launch path reads them once per process, the exports per call
+struct FfnKnobs {
+  int nw = 0;              // MOEINF_FFN_NW: waves per workgroup of the row kernel (0: by the rule in ffn_form)
+  int u = 0;               // MOEINF_FFN_U: its unroll (0: 4)
+  int nt = 0;              // MOEINF_FFN_NT: 1 = the row kernel at every size, > 1 = the grouped GEMMs at every size (0: by rows)
+  int many_rows = 16;      // MOEINF_FFN_MANY_ROWS: up to here the row kernel (decode)
+  int use_gemm = 2;        // MOEINF_FFN_GEMM: 0 = the row kernel's four-token-tile form, 1 = the register GEMM, 2 = by rows, 3 = hybrid
+  int gemm_nt = 0;         // MOEINF_FFN_GEMM_NT: token groups per pass of the register GEMM (0: 4)
+  int rgb_plain = 0;       // MOEINF_FFN_GEMM_RGB: row groups per LDS-kernel workgroup, plain stage (0: by the rule in ffn_form)
+  int rgb_gated = 4;       // MOEINF_FFN_GEMM_RGB2: ... gated stage
+  int big = 1;             // MOEINF_GEMM_BIG: 0 = never the 256 x 256 kernel
+  int big_rows = 256;      // MOEINF_GEMM_BIG_ROWS: the 256 x 256 kernel above
+  int hyb_rows = 0;        // MOEINF_GEMM_HYB_ROWS (0: 128 with <= 16 active experts, else 64)
+  int hyb_kk = 4;          // MOEINF_GEMM_HYB_KK: k-tiles per stage of the hybrid kernel (2 or 4)
+  int xl = 1;              // MOEINF_GEMM_XL: full-line activation staging (hybrid, LDS)
+  int wide = -1;           // MOEINF_GEMM_WIDE: the LDS kernel's 8 waves (-1: above 128 rows)
+  int ring2_bits = 3;      // MOEINF_GEMM_RING2: bit 0 gated stage, bit 1 plain stage
+  int ring2_min_k = 4096;  // MOEINF_RING_MIN_K
+  int ring2_max_rows = 340;  // MOEINF_RING2_MAX_ROWS: above, a second pass over the weights begins -> the big-tile kernel
+  int ring2_min_gated = 0;   // MOEINF_RING2_MIN_ROWS_GATED (0: where the hybrid kernel stops)
+  int ring2_min_plain = 16;  // MOEINF_RING2_MIN_ROWS_PLAIN
+  int ring2_tail = 1;        // MOEINF_RING2_TAIL: split a half-empty last round of the gated stage into half workgroups
+  static FfnKnobs from_env() {
+    auto env = [](const char* n, int d) { const char* v = getenv(n); return v && *v ? atoi(v) : d; };
+    FfnKnobs k;
+    k.nw = env("MOEINF_FFN_NW", k.nw); k.u = env("MOEINF_FFN_U", k.u); k.nt = env("MOEINF_FFN_NT", k.nt);
+    k.many_rows = env("MOEINF_FFN_MANY_ROWS", k.many_rows); k.use_gemm = env("MOEINF_FFN_GEMM", k.use_gemm);
+    k.gemm_nt = env("MOEINF_FFN_GEMM_NT", k.gemm_nt); k.rgb_plain = env("MOEINF_FFN_GEMM_RGB", k.rgb_plain);
+    k.rgb_gated = env("MOEINF_FFN_GEMM_RGB2", k.rgb_gated); k.big = env("MOEINF_GEMM_BIG", k.big);
+    k.big_rows = env("MOEINF_GEMM_BIG_ROWS", k.big_rows); k.hyb_rows = env("MOEINF_GEMM_HYB_ROWS", k.hyb_rows);
+    k.hyb_kk = env("MOEINF_GEMM_HYB_KK", k.hyb_kk); k.xl = env("MOEINF_GEMM_XL", k.xl); k.wide = env("MOEINF_GEMM_WIDE", k.wide);
+    k.ring2_bits = env("MOEINF_GEMM_RING2", k.ring2_bits); k.ring2_min_k = env("MOEINF_RING_MIN_K", k.ring2_min_k);
+    k.ring2_max_rows = env("MOEINF_RING2_MAX_ROWS", k.ring2_max_rows);
+    k.ring2_min_gated = env("MOEINF_RING2_MIN_ROWS_GATED", k.ring2_min_gated);
+    k.ring2_min_plain = env("MOEINF_RING2_MIN_ROWS_PLAIN", k.ring2_min_plain); k.ring2_tail = env("MOEINF_RING2_TAIL", k.ring2_tail);
     return k;
   }
 };
-// rows per expert up to which the hybrid kernel runs (17 ..): 128 when at most 16 experts are active, else 64
-inline int hyb_rows_for(int active, const Ring2Knobs& k) { return k.hyb_rows ? k.hyb_rows : (active <= 16 ? 128 : 64); }
+// rows per expert up to which the hybrid kernel runs (17 ..): 128 when at most 16 experts are active, else 64.  Measured: 17-64 rows
+// (e.g. NLLB's 128 experts at a 2048-token batch) are too many for the row kernel and too few to amortise staging the weights in
+// LDS (-15 % on that shape, sweep in profiles/); up to 128 rows with few active experts (big matrices, few workgroups — Mixtral at
+// 192 / 256 / 320 tokens: down projection 213 -> 174, 227 -> 208, 232 -> 226 us; with NLLB's 128 experts at 4096 tokens the same
+// switch costs +11 %)
+inline int hyb_rows_for(int active, const FfnKnobs& k) { return k.hyb_rows ? k.hyb_rows : (active <= 16 ? 128 : 64); }
+
 struct Ring2Form {
   int ntb = 0;    // 0: not ring2; else token groups per pass: 8 / 12 / 16 (128 / 192 / 256 tokens)
   int tail = 0;   // 1: 1-D grid with a split tail (gated stage only)
@@ -154,62 +182,164 @@ struct Ring2Form {
   int split = 0;  // first unit that is dealt to two half workgroups
   int blocks = 0; // workgroups launched
 };
-// elem_bytes: 2 (bf16 / fp16); f16: the hybrid kernel does not exist for fp16, the gated stage starts at 65 rows there;
-// row_groups = ceil(max(R, R_sh) / 16); active = grid.y (upper bound of experts with rows); max_rows: see launch_ffn_stage
-inline Ring2Form ring2_form(int elem_bytes, bool f16, int nmat, int K, int K_sh, int row_groups, int active, int max_rows, int num_cus,
-                            const Ring2Knobs& k) {
+// which form of ffn_gemm_ring2 a 2-byte stage takes.  f16: the gated stage starts at 65 rows there; row_groups = ceil(max(R, R_sh) /
+// 16); active = grid.y (upper bound of experts with rows); max_rows: see launch_ffn_stage
+inline Ring2Form ring2_form(bool f16, int nmat, int K, int K_sh, int row_groups, int active, int max_rows, int num_cus, const FfnKnobs& k) {
   Ring2Form f;
-  if (elem_bytes != 2 || !(k.enable_bits & (nmat == 2 ? 1 : 2))) return f;
-  const bool k_ok = (K % 64) == 0 && K >= k.min_k && (K_sh == 0 || ((K_sh % 64) == 0 && K_sh >= k.min_k));
-  const int min_rows = nmat == 2 ? (k.min_gated ? k.min_gated : (f16 ? 64 : hyb_rows_for(active, k))) : k.min_plain;
-  if (!k_ok || max_rows <= min_rows || max_rows > k.max_rows) return f;
+  if (!(k.ring2_bits & (nmat == 2 ? 1 : 2))) return f;
+  const bool k_ok = (K % 64) == 0 && K >= k.ring2_min_k && (K_sh == 0 || ((K_sh % 64) == 0 && K_sh >= k.ring2_min_k));
+  const int min_rows = nmat == 2 ? (k.ring2_min_gated ? k.ring2_min_gated : (f16 ? 64 : hyb_rows_for(active, k))) : k.ring2_min_plain;
+  if (!k_ok || max_rows <= min_rows || max_rows > k.ring2_max_rows) return f;
   f.ntb = max_rows <= 128 ? 8 : (max_rows <= 208 ? 12 : 16);
   f.nblk = (row_groups + 7) / 8;
   const int units = f.nblk * active, rem = num_cus > 0 ? units % num_cus : 0;
   f.blocks = units;
-  if (nmat == 2 && k.tail && units > num_cus && rem > 0 && rem <= num_cus / 2) {
+  if (nmat == 2 && k.ring2_tail && units > num_cus && rem > 0 && rem <= num_cus / 2) {
     f.tail = 1; f.split = units - rem; f.blocks = units + rem;
   }
   return f;
 }
 
-// ---- which grouped GEMM an fp8-slot stage takes (ffn_gemm_f8.hip): pure host logic, shared by launch_ffn_gemm_f8 and the export
-// moeinf_ffn_f8_gemm_form (engine.cpp), pinned by tests/test_fp8_gemm_selection_cpu.py against DESIGN.md section 4.3.  The bf16
-// thresholds and knobs, without the 256 x 256 kernel (not built for fp8): above ring2's rows the LDS-staged kernel's 8-wave form.
-struct F8GemmKnobs {
-  Ring2Knobs ring = Ring2Knobs::from_env();
-  int use_gemm = Ring2Knobs::env_or("MOEINF_FFN_GEMM", 2);         // 0: the row kernel's four-token-tile form; 3: always hybrid
-  int many_rows = Ring2Knobs::env_or("MOEINF_FFN_MANY_ROWS", 16);  // up to here: the row kernel (decode)
-  int wide = Ring2Knobs::env_or("MOEINF_GEMM_WIDE", -1);           // ffn_gemm_lds 8 waves (-1: above 128 rows)
+// what the choice reads from an FfnStage
+struct FfnShape {
+  int dtype = DT_BF16;       // activation dtype: DT_BF16, DT_F16, anything else runs as fp32
+  bool f8w = false;          // the routed experts' weights are an fp8 slot (FfnStage::wdtype == DT_F8)
+  int nmat = 1;              // 2: gated stage, 1: plain
+  int epi = EPI_NONE;
+  int K = 0, K_sh = 0;       // reduction lengths of the routed / shared experts (K_sh = 0: no shared expert in the launch)
+  int row_groups = 0;        // ceil(max(R, R_sh) / 16) = grid.x
+  bool out_aligned = true;   // ld_out % 8 == 0 (16-byte row stores)
+  bool rows_fit = true;      // rows_bound * ld_in fits in 32 bits (ring2 keeps element offsets into the activations in 32 bits)
+  bool fuse_combine = false;
+  int64_t row_bytes = 0;     // bytes of one weight row, the longer of the routed and the shared expert's
 };
-enum { F8G_ROWS = 0, F8G_HYB = 1, F8G_LDS = 2, F8G_RING2 = 3 };
-struct F8GemmForm {
-  int kernel = F8G_ROWS;
-  int width = 0;   // hyb / lds: waves per workgroup; ring2: token groups per pass (ring.ntb)
-  Ring2Form ring;  // kernel == F8G_RING2
-};
-// K_sh: the shared expert's reduction length, 0 without a shared expert in the launch (its weights are bf16: the hybrid and LDS
-// kernels give its workgroups the bf16 body; ring2's fp8 form takes routed experts only)
-inline F8GemmForm f8_gemm_form(int nmat, int K, int K_sh, int row_groups, int active, int max_rows, int num_cus, const F8GemmKnobs& k) {
-  F8GemmForm f;
-  if (max_rows <= k.many_rows || k.use_gemm == 0 || K % 64 != 0 || K_sh % 32 != 0) return f;
-  if (k.use_gemm != 3) {
-    if (K_sh == 0) {
-      f.ring = ring2_form(2, false, nmat, K, K_sh, row_groups, active, max_rows, num_cus, k.ring);
-      if (f.ring.ntb) { f.kernel = F8G_RING2; f.width = f.ring.ntb; return f; }
-    }
-    if (max_rows > hyb_rows_for(active, k.ring)) {
-      f.kernel = F8G_LDS;
-      f.width = (k.wide >= 0 ? k.wide != 0 : max_rows > 128) ? 8 : 4;
-      return f;
-    }
-  }
-  f.kernel = F8G_HYB; f.width = 4;
-  return f;
+inline FfnShape ffn_shape(const FfnStage& s) {
+  FfnShape h;
+  h.dtype = s.dtype;
+  h.f8w = s.wdtype == DT_F8;
+  h.nmat = (s.epi == EPI_GATED_SILU || s.epi == EPI_GATED_GELU) ? 2 : 1;
+  h.epi = s.epi;
+  h.K = s.K;
+  h.K_sh = s.R_sh > 0 ? s.K_sh : 0;
+  h.row_groups = ((s.R > s.R_sh ? s.R : s.R_sh) + 15) / 16;
+  h.out_aligned = s.ld_out % 8 == 0;
+  h.rows_fit = !(s.rows_bound > 0 && s.rows_bound * s.ld_in >= (int64_t(1) << 32));
+  h.fuse_combine = s.fuse_combine != 0;
+  h.row_bytes = (int64_t)(s.K > s.K_sh ? s.K : s.K_sh) * (h.f8w ? 1 : dt_bytes(s.dtype));
+  return h;
 }
 
-// max_rows_per_expert: upper bound of rows any one expert receives (selects the multi-token-tile variant)
-hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, hipStream_t st);
+// FFN_NONE: an fp8 stage no kernel takes (launch_ffn_stage: hipErrorInvalidValue).  The numbers are those of the exports.
+enum { FFN_NONE = -1, FFN_ROWS = 0, FFN_HYB = 1, FFN_LDS = 2, FFN_RING2 = 3, FFN_GEMM = 4, FFN_BIG = 5 };
+struct FfnForm {
+  int kernel = FFN_ROWS;  // ffn_rows_kernel | ffn_gemm_hyb_kernel | ffn_gemm_lds_kernel | ffn_gemm_ring2_kernel | ffn_gemm_kernel | ffn_gemm_big_kernel
+  int nmat = 1;           // matrices per stage (2: gated)
+  int waves = 0;          // per workgroup: rows 4 / 8 / 16, hybrid 4, LDS 4 / 8, register GEMM 4
+  int unroll = 0;         // rows with one token tile: 2 / 4 / 8
+  int nt = 0;             // token groups of 16 per pass: rows 1 / 4, register GEMM 4 / 8
+  int rw = 0;             // hybrid: row groups per wave
+  int kk = 0;             // hybrid: k-tiles per stage
+  int xl = 0;             // hybrid, LDS: full-line activation staging
+  int rgb = 0;            // LDS: row groups per workgroup
+  int passes = 0;         // big: passes over the tokens one launch holds (at most 8)
+  int num_cus = 0;        // big: compute units of the device (its short-pass rule)
+  Ring2Form ring;         // ring2
+};
+// active = grid.y (upper bound of experts with rows); max_rows: see launch_ffn_stage
+inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus, const FfnKnobs& k) {
+  FfnForm f;
+  f.nmat = s.nmat;
+  // fp8 slots: bf16 activations, whole fp8 tiles, and only the gated-SiLU and plain no-epilogue stages (Mixtral / DeepSeek)
+  if (s.f8w && (s.dtype != DT_BF16 || s.K % 64 != 0 || (s.epi != EPI_GATED_SILU && s.epi != EPI_NONE))) { f.kernel = FFN_NONE; return f; }
+  // the row kernel: long reductions get 8 waves per workgroup (more bytes in flight per CU), short ones 4 ... and a grid of at most
+  // one workgroup per CU (Switch-base-8 at batch 1: 192 / 48 workgroups for 256 CUs) SIXTEEN: a CU that owns a single work item has
+  // nothing else to hide its load latency behind, so the whole item goes in flight at once (round 4: stage 2 of Switch-base-8
+  // streamed 9.45 MB in 16.8 us = 0.07 of HBM peak with 48 four-wave workgroups)
+  const bool few = (int64_t)s.row_groups * active <= 256 && s.row_bytes / 64 >= 32 && !s.fuse_combine;
+  const int nw = k.nw ? k.nw : (few ? 16 : (s.row_bytes >= 16384 ? 8 : 4));
+  // it re-streams an expert's weights for every 16 rows: from 17 rows on, the GEMM kernels (one pass per 128/256 rows) win —
+  // Mixtral at 64 tokens: 761 -> 549 us per layer (profiles/r01_ffn_sweep_midsize.txt)
+  const bool many = !s.fuse_combine && (k.nt ? k.nt > 1 : max_rows > k.many_rows);
+  if (!many) {
+    const int u = k.u ? k.u : 4;
+    f.nt = 1;
+    f.waves = nw == 16 || nw == 8 ? nw : 4;
+    f.unroll = nw != 16 && (u == 2 || u == 8) ? u : 4;
+    return f;
+  }
+  // what the grouped GEMMs below decline: the row kernel looping four token tiles
+  f.nt = 4;
+  f.waves = nw == 8 ? 8 : 4;
+  // the grouped GEMMs are built for the SiLU gate only: the gelu gate runs the row kernel at every size
+  if (s.epi == EPI_GATED_GELU) return f;
+  const int ept = (s.dtype == DT_BF16 || s.dtype == DT_F16) ? 32 : 16;  // activation elements per 64-byte k-tile
+  const bool k_ok = s.K % ept == 0 && s.K_sh % ept == 0;
+  int use_gemm = k.use_gemm;
+  if (s.f8w) {
+    // fp8: up to MOEINF_FFN_MANY_ROWS the row kernel even where a forced MOEINF_FFN_NT > 1 sends bf16 into the GEMMs (kept as it was).
+    // No fp8 register GEMM: where bf16 takes it for a reduction that is not whole k-tiles (K_sh % 32), fp8 takes the row kernel.
+    if (max_rows <= k.many_rows || !k_ok) return f;
+    // kept as it was: under MOEINF_FFN_GEMM=1 (any value but 0 and 3) fp8 takes the hybrid / LDS / ring2 choice, bf16 the register GEMM
+    if (use_gemm != 0 && use_gemm != 3) use_gemm = 2;
+  }
+  FfnForm g;
+  g.nmat = s.nmat;
+  // long reductions (K >= 4096: Mixtral's two stages, NLLB's second), 17 (plain) / hyb_rows+1 (gated) .. 340 rows per expert: the
+  // software-pipelined register ring (ring2_form).  Measured against what ran there before (profiles/r04_ffn_sweep_ring2_*.txt,
+  // Mixtral-8x7B, us per layer, gate-up / down):
+  //   tokens   96       224       336       384       512       640       768       896
+  //   before   320/162  337/196   365/233   404/252   441/261   494/274   492/342   510/347   (hybrid | ring + lds | big)
+  //   ring2    (hyb)/147 (hyb)/157 (hyb)/173 347/178   374/202   401/233   438/256   487/287
+  // gated stage below 129 rows: the hybrid kernel is 1-2 % ahead and stays.  Above ~256 rows per expert (the row estimate of the
+  // sync-free path is 1.5 x the mean + 1 = 337 at 896 tokens, 385 at 1 024) a second pass over the weights begins and the big-tile
+  // kernel takes over.  An expert with more rows than a pass holds takes another pass; correctness never depends on the estimate.
+  // Kept as it was: fp16 tries the ring before it looks at MOEINF_FFN_GEMM.  fp8: ring2's fp8 form takes routed experts only (the
+  // shared expert's weights are bf16), so not with a shared expert in the launch.
+  const bool ring = s.f8w ? use_gemm == 2 && s.K_sh == 0 : (s.dtype == DT_F16 || (s.dtype == DT_BF16 && use_gemm == 2));
+  if (ring && s.rows_fit) {
+    g.ring = ring2_form(s.dtype == DT_F16, s.nmat, s.K, s.K_sh, s.row_groups, active, max_rows, num_cus, k);
+    if (g.ring.ntb) { g.kernel = FFN_RING2; return g; }
+  }
+  // long prefills: the 256 x 256 / 32x32x16-MFMA kernel (ffn_gemm_big.hip; bf16 and fp16 — no fp8 form; 16-byte row stores).
+  // Measured (profiles/r03_ffn_sweep_prefill_big_*.txt): it beats ffn_gemm_lds from 257 rows per expert on (Mixtral down projection
+  // at 2048 tokens 846 -> 730 us, DeepSeek-V2-Lite at 4096 tokens 2.54 -> 1.96 ms per layer).  The register-ring kernel (gated
+  // stage, K >= 4096) held out to ~640 rows against the first ping-pong version; with the short-last-pass variant the big kernel
+  // wins from 257 rows on (Mixtral gate/up: 768 tokens 503 vs 535 us, 1024 tokens 647 vs 748, 1536 tokens 845 vs 1 031, 2048
+  // tokens 1 010 vs 1 250), so both stages switch at the same row count now; below it (512 tokens: 436 vs 450 gate/up but 324 vs
+  // 265 down) ring / lds stay
+  if (use_gemm == 2 && k.big && !s.f8w && (s.dtype == DT_BF16 || s.dtype == DT_F16) && max_rows > k.big_rows && s.K % 64 == 0 &&
+      s.K_sh % 64 == 0 && s.out_aligned) {
+    const int passes = max_rows <= 256 ? 1 : (max_rows + 255) / 256;
+    g.kernel = FFN_BIG; g.passes = passes > 8 ? 8 : passes; g.num_cus = num_cus;
+    return g;
+  }
+  const bool xl = k.xl && s.K % (2 * ept) == 0 && s.K_sh % (2 * ept) == 0;
+  if ((use_gemm == 3 || (use_gemm == 2 && max_rows <= hyb_rows_for(active, k))) && k_ok) {  // weights -> registers, activations -> LDS
+    g.kernel = FFN_HYB; g.waves = 4; g.rw = s.nmat == 2 ? 1 : 2; g.kk = k.hyb_kk == 2 ? 2 : 4; g.xl = xl;
+  } else if (use_gemm == 2 && k_ok) {  // LDS-staged
+    g.kernel = FFN_LDS;
+    g.waves = (k.wide >= 0 ? k.wide != 0 : max_rows > 128) ? 8 : 4;  // 8 waves: 256 tokens per pass over the weights
+    // plain stage: 128-row blocks need >= 2 blocks per CU to hide the DMA latency; 64-row blocks otherwise
+    const bool rows128 = s.nmat == 2 ? k.rgb_gated == 8 : (k.rgb_plain ? k.rgb_plain == 8 : ((s.row_groups + 7) / 8) * active >= 512 && s.K >= 4096);
+    g.rgb = rows128 ? 8 : 4; g.xl = xl;
+  } else if (use_gemm) {  // the register GEMM (never fp8: k_ok)
+    // measured: (RG,NT)=(2,4)/(4,4) beats (1,8)/(2,8) at t_e ~128 (profiles/r01_ffn_sweep_prefill_gemm.txt)
+    g.kernel = FFN_GEMM; g.waves = 4; g.nt = (k.gemm_nt ? k.gemm_nt : 4) <= 4 ? 4 : 8;
+  } else {
+    return f;
+  }
+  return g;
+}
+
+// max_rows_per_expert: upper bound of rows any one expert receives (selects the kernel and its form); num_cus: of the device
+hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st);
+// the grouped GEMMs, one launcher per translation unit: each maps the form ffn_form chose to its instantiation
+void launch_ffn_gemm(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);             // ffn_gemm.hip: bf16, fp32
+void launch_ffn_gemm_f16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);         // ffn_gemm_f16.hip
+void launch_ffn_gemm_f8(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);          // ffn_gemm_f8.hip: fp8 slots
+void launch_ffn_gemm_ring2_bf16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);  // ffn_gemm_ring2.hip
+void launch_ffn_gemm_ring2_f16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);   // ffn_gemm_ring2_f16.hip
+void launch_ffn_gemm_big(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);         // ffn_gemm_big.hip: bf16, fp16
 // row-major [R,K] -> MFMA A-operand tiles (see kernels.hip); dst needs tiled_bytes(R,K) bytes
 hipError_t launch_retile(const void* src, void* dst, int R, int K, int dtype, hipStream_t st);
 // all tensors of one staged blob in one launch: tensor t = (src + src_off[t]) row-major [R, K] -> (dst + dst_off[t]) tiled;

@@ -292,82 +292,41 @@ __global__ __launch_bounds__(NW * 64) void ffn_rows_kernel(FfnStage s) {
 }
 
 
-// grouped GEMM variants for experts with many rows (ffn_gemm.hip); false: not handled (MOEINF_FFN_GEMM=0)
+// the row kernel in the form ffn_form chose (T = uint16_t, half_t, float, f8w_t)
 template <typename T, int NMAT>
-bool launch_ffn_gemm(const FfnStage& s, dim3 grid, int max_rows, hipStream_t st);
-bool launch_ffn_gemm_big(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);  // ffn_gemm_big.hip (bf16, fp16)
-bool launch_ffn_gemm_ring2_f16(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);  // ffn_gemm.hip
-
-template <typename T, int NMAT>
-static void launch_ffn_t(const FfnStage& s, dim3 grid, int nw, int u, bool many_tokens, int max_rows, hipStream_t st) {
+static void launch_ffn_rows(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st) {
 #define LAUNCH(NWV, UU, NTT) KL((ffn_rows_kernel<T, NMAT, NWV, UU, NTT>), grid, dim3(NWV * 64), 0, st, s)
-  if (many_tokens) {  // grouped GEMM kernels (ffn_gemm.hip); MOEINF_FFN_GEMM=0: the decode kernel looping 4 token tiles
-    if constexpr (sizeof(T) == 2 && !std::is_same<T, uint16_t>::value) {
-      // fp16 experts: the register ring first (long reductions, up to 340 rows per expert; its own translation unit), then
-      // the same choice between the hybrid / LDS-staged / 256 x 256 kernels as bf16 (ffn_gemm_f16.hip, round 5)
-      if (launch_ffn_gemm_ring2_f16(s, NMAT, grid, max_rows, st)) return;
-      if (launch_ffn_gemm<T, NMAT>(s, grid, max_rows, st)) return;
-    } else {
-      if (launch_ffn_gemm<T, NMAT>(s, grid, max_rows, st)) return;
-    }
-    if (nw == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4);
-    return;
-  }
-  if (nw == 16) { LAUNCH(16, 4, 1); }
-  else if (nw == 8) { if (u == 2) LAUNCH(8, 2, 1); else if (u == 8) LAUNCH(8, 8, 1); else LAUNCH(8, 4, 1); }
-  else         { if (u == 2) LAUNCH(4, 2, 1); else if (u == 8) LAUNCH(4, 8, 1); else LAUNCH(4, 4, 1); }
+  if (f.nt == 4) { if (f.waves == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4); }
+  else if (f.waves == 16) { LAUNCH(16, 4, 1); }
+  else if (f.waves == 8) { if (f.unroll == 2) LAUNCH(8, 2, 1); else if (f.unroll == 8) LAUNCH(8, 8, 1); else LAUNCH(8, 4, 1); }
+  else         { if (f.unroll == 2) LAUNCH(4, 2, 1); else if (f.unroll == 8) LAUNCH(4, 8, 1); else LAUNCH(4, 4, 1); }
 #undef LAUNCH
 }
 
-bool launch_ffn_gemm_f8(const FfnStage& s, int nmat, dim3 grid, int max_rows, hipStream_t st);  // ffn_gemm_f8.hip
-
-// fp8 slots: up to 16 rows per expert the row kernel; more rows take the fp8 forms of the grouped GEMMs (ffn_gemm_f8.hip, chosen by
-// f8_gemm_form).  The row kernel's four-token-tile form is left for what they decline: MOEINF_FFN_GEMM=0 (as for bf16), a
-// shared expert whose reduction is not a multiple of 32, a forced MOEINF_FFN_NT with <= 16 rows
-template <int NMAT>
-static void launch_ffn_f8w(const FfnStage& s, dim3 grid, int nw, int u, bool many_tokens, int max_rows, hipStream_t st) {
-#define LAUNCH(NWV, UU, NTT) KL((ffn_rows_kernel<f8w_t, NMAT, NWV, UU, NTT>), grid, dim3(NWV * 64), 0, st, s)
-  if (many_tokens) {
-    if (launch_ffn_gemm_f8(s, NMAT, grid, max_rows, st)) return;
-    if (nw == 8) LAUNCH(8, 1, 4); else LAUNCH(4, 1, 4);
-    return;
-  }
-  if (nw == 16) { LAUNCH(16, 4, 1); }
-  else if (nw == 8) { if (u == 2) LAUNCH(8, 2, 1); else if (u == 8) LAUNCH(8, 8, 1); else LAUNCH(8, 4, 1); }
-  else         { if (u == 2) LAUNCH(4, 2, 1); else if (u == 8) LAUNCH(4, 8, 1); else LAUNCH(4, 4, 1); }
-#undef LAUNCH
-}
-
-hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, hipStream_t st) {
-  static const int env_nw = env_int("MOEINF_FFN_NW", 0), env_u = env_int("MOEINF_FFN_U", 0);
-  const int rmax = s.R > s.R_sh ? s.R : s.R_sh;
-  dim3 grid((rmax + 15) / 16, max_active);
-  const bool gated = (s.epi == EPI_GATED_SILU || s.epi == EPI_GATED_GELU);
-  // long reductions get 8 waves per block (more bytes in flight per CU), short ones 4
-  const int kmax = s.K > s.K_sh ? s.K : s.K_sh;
-  const bool f8w = s.wdtype == DT_F8;
-  if (f8w && (s.dtype != DT_BF16 || s.K % 64 != 0 || (s.epi != EPI_GATED_SILU && s.epi != EPI_NONE))) return hipErrorInvalidValue;
-  const size_t kbytes = (size_t)kmax * (f8w ? 1 : dt_bytes(s.dtype));  // (routed weight bytes per row)
-  // ... and a grid of at most one workgroup per CU (Switch-base-8 at batch 1: 192 / 48 workgroups for 256 CUs) SIXTEEN: a CU
-  // that owns a single work item has nothing else to hide its load latency behind, so the whole item goes in flight at
-  // once (round 4: stage 2 of Switch-base-8 streamed 9.45 MB in 16.8 us = 0.07 of HBM peak with 48 four-wave workgroups)
-  const int kb_tiles = (int)(kbytes / 64);
-  const bool few = (int64_t)grid.x * grid.y <= 256 && kb_tiles >= 32 && !s.fuse_combine;
-  const int nw = env_nw ? env_nw : (few ? 16 : (kbytes >= 16384 ? 8 : 4));
-  const int u = env_u ? env_u : 4;
-  static const int env_nt = env_int("MOEINF_FFN_NT", 0);
-  // the decode kernel re-streams an expert's weights for every 16 rows: from 17 rows on, the GEMM kernels (one pass
-  // per 128/256 rows) win — Mixtral at 64 tokens: 761 -> 549 us per layer (profiles/r01_ffn_sweep_midsize.txt)
-  static const int many_rows = env_int("MOEINF_FFN_MANY_ROWS", 16);
-  const bool many = s.fuse_combine ? false : (env_nt ? env_nt > 1 : max_rows_per_expert > many_rows);
-  if (f8w) {
-    if (gated) launch_ffn_f8w<2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_f8w<1>(s, grid, nw, u, many, max_rows_per_expert, st);
-  } else if (s.dtype == DT_BF16) {
-    if (gated) launch_ffn_t<uint16_t, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<uint16_t, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
-  } else if (s.dtype == DT_F16) {
-    if (gated) launch_ffn_t<half_t, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<half_t, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
-  } else {
-    if (gated) launch_ffn_t<float, 2>(s, grid, nw, u, many, max_rows_per_expert, st); else launch_ffn_t<float, 1>(s, grid, nw, u, many, max_rows_per_expert, st);
+hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st) {
+  static const FfnKnobs knobs = FfnKnobs::from_env();
+  const FfnShape h = ffn_shape(s);
+  const FfnForm f = ffn_form(h, max_active, max_rows_per_expert, num_cus, knobs);
+  const dim3 grid(h.row_groups, max_active);
+  const bool gated = f.nmat == 2;
+  switch (f.kernel) {
+    case FFN_NONE: return hipErrorInvalidValue;
+    case FFN_ROWS:
+      if (h.f8w) { if (gated) launch_ffn_rows<f8w_t, 2>(s, grid, f, st); else launch_ffn_rows<f8w_t, 1>(s, grid, f, st); }
+      else if (s.dtype == DT_BF16) { if (gated) launch_ffn_rows<uint16_t, 2>(s, grid, f, st); else launch_ffn_rows<uint16_t, 1>(s, grid, f, st); }
+      else if (s.dtype == DT_F16) { if (gated) launch_ffn_rows<half_t, 2>(s, grid, f, st); else launch_ffn_rows<half_t, 1>(s, grid, f, st); }
+      else { if (gated) launch_ffn_rows<float, 2>(s, grid, f, st); else launch_ffn_rows<float, 1>(s, grid, f, st); }
+      break;
+    case FFN_BIG: launch_ffn_gemm_big(s, grid, f, st); break;
+    case FFN_RING2:
+      if (h.f8w) launch_ffn_gemm_f8(s, grid, f, st);
+      else if (s.dtype == DT_F16) launch_ffn_gemm_ring2_f16(s, grid, f, st);
+      else launch_ffn_gemm_ring2_bf16(s, grid, f, st);
+      break;
+    default:  // hybrid, LDS-staged, register GEMM
+      if (h.f8w) launch_ffn_gemm_f8(s, grid, f, st);
+      else if (s.dtype == DT_F16) launch_ffn_gemm_f16(s, grid, f, st);
+      else launch_ffn_gemm(s, grid, f, st);
   }
   return hipGetLastError();
 }

@@ -70,7 +70,9 @@ int main(int argc, char** argv) {
     printf("%-58s %7.2f us  %7.1f GB/s\n", name, us, mb * 1e6 / us / 1e3);
   };
   const double mb1 = (2.0 * F * H * 2 * K + (with_shared ? 2.0 * Fs * H * 2 : 0)) / 1e6, mb2 = (1.0 * F * H * 2 * K + (with_shared ? 1.0 * Fs * H * 2 : 0)) / 1e6;
-  auto L = [&](FfnStage st, int s) { st.wptr = wptr + (size_t)s * (E + 1); CK(launch_ffn_stage(st, nact, 1, nullptr)); };
+  int ncu = 0;
+  CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
+  auto L = [&](FfnStage st, int s) { st.wptr = wptr + (size_t)s * (E + 1); CK(launch_ffn_stage(st, nact, 1, ncu, nullptr)); };
   run("stage 1 (gate+up, fused silu*mul)", mb1, [&](int s) { L(s1, s); });
   run("stage 2 (down)", mb2, [&](int s) { L(s2, s); });
   run("stage 2 + fused combine", mb2, [&](int s) { L(s2f, s); });
