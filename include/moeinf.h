@@ -44,6 +44,10 @@ enum { MOEINF_DTYPE_BF16 = 0, MOEINF_DTYPE_F32 = 1, MOEINF_DTYPE_F16 = 2,
         * slot; activations, gate and arithmetic are bf16 — y = FFN(x; W.to(bf16)) (round 6).  With fp8 slots (moeinf_create_ex,
         * slot_dtype = MOEINF_DTYPE_F8E4M3) they stay fp8 in the slot too and the FFN kernels up-cast in registers: same y */
        MOEINF_DTYPE_F8E4M3 = 3 };
+/* NOT a dtype id (cfg->dtype = 4.. stays refused): a value of moeinf_create_options.slot_dtype only — the routed experts are OCP
+ * MXFP4 (e2m1 elements, one e8m0 scale per 32 consecutive elements of a row) in the host tier, on the link and in their HBM slots
+ * ("MXFP4 slots", see moeinf_create_ex).  moeinf_slot_dtype reports it; moeinf_ffn_form takes it as its dtype argument. */
+enum { MOEINF_SLOT_MXFP4 = 16 };
 
 /* expert_type ids: core/parallel/expert_module.h:13-18, moe_infinity/common/constants.py:29-37 */
 enum {
@@ -144,7 +148,8 @@ int moeinf_rows_estimate(int tokens, int top_k, int num_experts);
 /* ---- introspection for tests (no reference counterpart, no GPU needed): which kernel, and which form of it, the launcher picks
  * for an FFN stage.  One function decides for every dtype (csrc/kernels.h ffn_form); these exports report
  * what it gives, with the environment knobs as they are at the call (the launcher reads them once per process).
- * dtype: MOEINF_DTYPE_*, MOEINF_DTYPE_F8E4M3 = an fp8 slot (bf16 activations, fp8 routed weights); epi: the stage's epilogue
+ * dtype: MOEINF_DTYPE_*, MOEINF_DTYPE_F8E4M3 = an fp8 slot (bf16 activations, fp8 routed weights), MOEINF_SLOT_MXFP4 = an MXFP4
+ * slot (bf16 activations, MXFP4 routed weights: the row kernel at every row count, K % 128 == 0); epi: the stage's epilogue
  * (csrc/kernels.h EPI_*: 0 none, 1 bias, 2 relu, 3 bias + relu, 4 gated SiLU, 5 gated GELU; 4 and 5 are the gated stage);
  * K / K_sh: reduction length of the routed / shared experts (K_sh = 0: no shared expert rides in the launch); R: output rows
  * (the larger of the routed and the shared expert's); active: experts with rows (the grid's upper bound); max_rows: rows of the
@@ -186,7 +191,22 @@ int moeinf_destroy(moeinf_engine* eng);
  * bf16 slots.  Accepted for Mixtral / DeepSeek experts (routers: Mixtral, softmax-top-k, DeepSeek, DeepSeek-V3), ep_size == 1,
  * hidden % 64 == 0 and inter % 64 == 0; anything else is MOEINF_ERR_UNSUPPORTED with the reason.  Stages with more than 16
  * rows per expert (prefill) run fp8-weight forms of the grouped GEMMs (hybrid, LDS-staged, register ring; moeinf_ffn_f8_gemm_form
- * says which); there is no fp8 form of the 256 x 256 kernel, so above 340 rows per expert the LDS-staged kernel runs. */
+ * says which); there is no fp8 form of the 256 x 256 kernel, so above 340 rows per expert the LDS-staged kernel runs.
+ * MOEINF_SLOT_MXFP4 ("MXFP4 slots"): accepted only with cfg->dtype == MOEINF_DTYPE_BF16 (gate_dtype bf16 or fp32).  The routed
+ * experts are MXFP4 everywhere below the caller: 4.25 bits per weight in the pinned arena, the offload directory, on the link and in
+ * the slot (about 0.266 of bf16's bytes, so about 3.7 x the experts per device budget); the decode FFN kernels stream the codes and
+ * scales and up-cast in registers (v_cvt_scalef32_pk_bf16_fp4).  e2m1 x 2^n is exact in bf16, so y = FFN(x; dequant(W).to(bf16)):
+ * what a bf16 engine computes on the dequantised weights.  HOST BLOB: the family's tensors in the usual order (mixtral w1 w2 w3,
+ * deepseek gate up down), each padded to 4 KiB; a matrix W[R, K] is ONE tensor = its packed codes, [R, K/2] bytes row-major,
+ * element 2j of a row in the LOW nibble of byte j (torch.float4_e2m1fn_x2's convention; code = sign bit 3, exponent bits 2..1,
+ * mantissa bit 0: 0 0.5 1 1.5 2 3 4 6), followed at once by its scales, [R, K/32] bytes row-major, byte b = 2^(b - 127) for elements
+ * 32i .. 32i+31 of the row.  Scale bytes 0 and 255 (2^-127, NaN) are OUTSIDE the contract: the result for a block that carries one
+ * is unspecified (moe_infinity_amd.quant.mxfp4_quantize never emits them).  moeinf_expert_layout reports these tensors.  DeepSeek's
+ * shared expert stays bf16 (its blob and moeinf_register_shared are a bf16 engine's).  Accepted for Mixtral / DeepSeek experts
+ * under the routers fp8 slots accept, ep_size == 1, hidden % 128 == 0, inter % 128 == 0 (and reductions the tier mover's scale units
+ * hold: up to 8192, 16384 with K/128 even, 32768 with K/128 a multiple of 4), with the pull tier mover (not MOEINF_H2D_PULL=0);
+ * anything else is MOEINF_ERR_UNSUPPORTED with a message that names mxfp4 and the reason.  Every row count runs the row kernel
+ * (four token tiles per pass above 16 rows per expert); MXFP4 forms of the grouped GEMMs are not built. */
 typedef struct moeinf_create_options {
   int32_t struct_bytes;
   int32_t slot_dtype;

@@ -68,6 +68,9 @@ class EpProfile(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+SLOT_MXFP4 = 16  # MOEINF_SLOT_MXFP4: a value of CreateOptions.slot_dtype, not a dtype id
+
+
 class CreateOptions(C.Structure):  # moeinf_create_options (creation options outside the ABI-4 config struct)
     _fields_ = [("struct_bytes", C.c_int32), ("slot_dtype", C.c_int32), ("reserved", C.c_int32 * 6)]
 

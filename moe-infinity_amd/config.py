@@ -15,6 +15,8 @@ DTYPE_BF16, DTYPE_F32, DTYPE_F16 = 0, 1, 2
 # to bf16 as they are pulled into their HBM slot.  EngineConfig.fp8_slots: they stay fp8 in the slot (half the bytes: about twice the
 # experts per device budget) and the FFN kernels up-cast in registers
 DTYPE_F8E4M3 = 3
+# what MoEEngine.slot_dtype reports for EngineConfig.mxfp4_slots (MOEINF_SLOT_MXFP4): a slot kind, never a `dtype`
+SLOT_MXFP4 = 16
 EXPERT_SWITCH, EXPERT_SWITCH_GATED, EXPERT_NLLB, EXPERT_FSGPT, EXPERT_MIXTRAL, EXPERT_DEEPSEEK = 0, 1, 2, 3, 4, 5
 ROUTER_MIXTRAL, ROUTER_DEEPSEEK, ROUTER_SWITCH, ROUTER_NLLB, ROUTER_SOFTMAX_TOPK, ROUTER_DEEPSEEK_V3 = 0, 1, 2, 3, 4, 5
 POLICY_LFU_INCACHE, POLICY_LRU = 0, 1
@@ -83,6 +85,14 @@ class EngineConfig:
     # fp8 experts (dtype DTYPE_F8E4M3) keep fp8 in their HBM slots (moeinf_create_ex): Mixtral / DeepSeek experts, ep_size 1,
     # hidden and inter multiples of 64.  Not part of the C config struct.
     fp8_slots: bool = False
+    # a bf16 engine (dtype DTYPE_BF16) whose routed experts are OCP MXFP4 — (codes, scales) pairs from quant.mxfp4_quantize — in the
+    # host tier, on the link and in their HBM slots (moeinf_create_ex, MOEINF_SLOT_MXFP4): y = FFN(x; dequant(W).to(bf16)).  Mixtral /
+    # DeepSeek experts, ep_size 1, hidden and inter multiples of 128.  Not part of the C config struct.
+    mxfp4_slots: bool = False
+
+    def __post_init__(self):
+        if self.fp8_slots and self.mxfp4_slots:
+            raise ValueError("fp8_slots and mxfp4_slots are two different slot formats: set one")
 
     def to_dict(self):
         return asdict(self)

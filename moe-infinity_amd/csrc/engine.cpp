@@ -76,8 +76,8 @@ extern "C" int moeinf_fence_cover_pos(const uint64_t* fence_seq, uint64_t record
 static moeinf::FfnForm ffn_form_of(int dtype, int epi, int K, int K_sh, int R, int active, int max_rows, int num_cus, int flags) {
   moeinf::FfnStage s;
   memset(&s, 0, sizeof s);
-  const bool f8w = dtype == MOEINF_DTYPE_F8E4M3;
-  s.dtype = f8w ? moeinf::DT_BF16 : dtype; s.wdtype = f8w ? moeinf::DT_F8 : dtype;
+  const bool f8w = dtype == MOEINF_DTYPE_F8E4M3, mx4w = dtype == MOEINF_SLOT_MXFP4;
+  s.dtype = (f8w || mx4w) ? moeinf::DT_BF16 : dtype; s.wdtype = f8w ? moeinf::DT_F8 : (mx4w ? moeinf::DT_MX4 : dtype);
   s.epi = epi; s.K = K; s.R = R; s.K_sh = K_sh; s.R_sh = K_sh > 0 ? R : 0;
   s.ld_in = 1; s.ld_out = (flags & 1) ? 4 : 8; s.rows_bound = (flags & 2) ? int64_t(1) << 32 : 0; s.fuse_combine = (flags & 4) ? 1 : 0;
   return moeinf::ffn_form(moeinf::ffn_shape(s), active, max_rows, num_cus, moeinf::FfnKnobs::from_env());
@@ -267,8 +267,9 @@ extern "C" int moeinf_destroy(moeinf_engine* g) {
 }
 
 static void prealloc_slots(moeinf_engine* g);
-static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine** out);
-extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, false, out); }
+enum SlotKind { SLOT_PLAIN = 0, SLOT_F8 = 1, SLOT_MX4 = 2 };  // what moeinf_create_ex asked the routed experts' slots to hold
+static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine** out);
+extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, SLOT_PLAIN, out); }
 
 // fp8 slots: what the fp8-weight kernels cover (kernels.hip / layer_fused.hip: the row-dot forms of the gated families); every
 // other configuration is refused here, so the kernels that have no fp8 form (ffn_form picks no such grouped GEMM; the
@@ -285,27 +286,54 @@ static int check_fp8_slots(const moeinf_config* c) {
     return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need hidden and inter to be multiples of 64 (one fp8 tile: 64 k), not %d / %d", c->hidden, c->inter);
   return MOEINF_OK;
 }
+// MXFP4 slots: a bf16 engine whose routed experts are OCP MXFP4 in the host tier, on the link and in their slots; decided here,
+// before any device call.  What the MXFP4-weight kernels cover is what the fp8-weight row-dot kernels cover, on 128-k tiles.
+static int check_mxfp4_slots(const moeinf_config* c) {
+  if (c->dtype != MOEINF_DTYPE_BF16) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots need a bf16 engine (dtype %d, not %d): the experts are up-cast to bf16 in registers", MOEINF_DTYPE_BF16, c->dtype);
+  if (c->gate_dtype != MOEINF_DTYPE_BF16 && c->gate_dtype != MOEINF_DTYPE_F32) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: gate_dtype %d is neither bf16 nor fp32", c->gate_dtype);
+  if (c->expert_type != MOEINF_EXPERT_MIXTRAL && c->expert_type != MOEINF_EXPERT_DEEPSEEK)
+    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are built for Mixtral and DeepSeek experts only (expert_type %d)", c->expert_type);
+  if (c->router_kind != MOEINF_ROUTER_MIXTRAL && c->router_kind != MOEINF_ROUTER_SOFTMAX_TOPK && c->router_kind != MOEINF_ROUTER_DEEPSEEK &&
+      c->router_kind != MOEINF_ROUTER_DEEPSEEK_V3)
+    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: router_kind %d is not one of the Mixtral / DeepSeek families'", c->router_kind);
+  if (c->ep_size != 1) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are not built for expert parallelism (ep_size %d)", c->ep_size);
+  if (c->hidden <= 0 || c->inter <= 0 || c->hidden % 128 || c->inter % 128)
+    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots need hidden and inter to be multiples of 128 (one mxfp4 tile: 128 k), not %d / %d", c->hidden, c->inter);
+  // the tier mover re-orders the scales of whole row groups through 16 KiB of LDS (kernels.hip: mx4_scale_groups)
+  for (int K : {c->hidden, c->inter}) {
+    const int KB = K / 128, ga = (KB % 4 == 0) ? 1 : ((KB % 2 == 0) ? 2 : 4);
+    if (ga * KB * 64 > 16384) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: a reduction length of %d is too long for the tier mover's scale units", K);
+  }
+  const char* pe = getenv("MOEINF_H2D_PULL");
+  if (pe && atoi(pe) == 0) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are filled by the PULL tier mover: not with MOEINF_H2D_PULL=0");
+  return MOEINF_OK;
+}
 extern "C" int moeinf_create_ex(const moeinf_config* cfg, const moeinf_create_options* opts, moeinf_engine** out) {
   if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!cfg) return fail(MOEINF_ERR_INVALID, "cfg is NULL");
-  if (!opts) return create_engine(cfg, false, out);
+  if (!opts) return create_engine(cfg, SLOT_PLAIN, out);
   if (opts->struct_bytes != (int32_t)sizeof(moeinf_create_options)) return fail(MOEINF_ERR_INVALID, "options.struct_bytes %d != %d", opts->struct_bytes, (int)sizeof(moeinf_create_options));
   for (int i = 0; i < 6; ++i) if (opts->reserved[i]) return fail(MOEINF_ERR_INVALID, "options.reserved[%d] must be zero", i);
+  if (opts->slot_dtype == MOEINF_SLOT_MXFP4) {
+    CHK(check_mxfp4_slots(cfg));
+    return create_engine(cfg, SLOT_MX4, out);
+  }
   // (fp8 experts: slot_dtype bf16 = today's engine, the pull kernel up-casts into bf16 slots)
   const bool plain = opts->slot_dtype == cfg->dtype || (cfg->dtype == MOEINF_DTYPE_F8E4M3 && opts->slot_dtype == MOEINF_DTYPE_BF16);
-  if (plain && opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return create_engine(cfg, false, out);
+  if (plain && opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return create_engine(cfg, SLOT_PLAIN, out);
   if (opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "slot_dtype %d with dtype %d: only fp8 slots (%d) for fp8 experts are built", opts->slot_dtype, cfg->dtype, MOEINF_DTYPE_F8E4M3);
   CHK(check_fp8_slots(cfg));
-  return create_engine(cfg, true, out);
+  return create_engine(cfg, SLOT_F8, out);
 }
 extern "C" int moeinf_slot_dtype(const moeinf_engine* g, int32_t* slot_dtype) {
   if (!g || !slot_dtype) return fail(MOEINF_ERR_INVALID, "engine or slot_dtype is NULL");
-  *slot_dtype = g->slot_f8 ? MOEINF_DTYPE_F8E4M3 : g->cfg.dtype;
+  *slot_dtype = g->slot_mx4 ? MOEINF_SLOT_MXFP4 : (g->slot_f8 ? MOEINF_DTYPE_F8E4M3 : g->cfg.dtype);
   return MOEINF_OK;
 }
 
-static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine** out) {
+static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine** out) {
+  const bool slot_f8 = slot == SLOT_F8, slot_mx4 = slot == SLOT_MX4;
   if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
   *out = nullptr;
   // fp8 experts (the reference's dtype id 3, core/parallel/expert_module.h:23,118-119): e4m3fn bytes in the HOST tier and on the link,
@@ -343,11 +371,12 @@ static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine**
   g->es = dt_bytes(g->dt);
   g->host_f8 = host_f8;
   g->host_es = host_f8 ? 1 : g->es;
-  g->lay = make_layout(cfg->expert_type, g->H, g->F, g->host_es);
+  g->slot_mx4 = slot_mx4;  // (never with fp8 experts: check_mxfp4_slots refused them)
+  g->lay = make_layout(cfg->expert_type, g->H, g->F, g->host_es, g->slot_mx4);
   if (g->has_shared) g->lay_sh = make_layout(cfg->expert_type, g->H, g->Fs, g->host_es);
   // fp8 slots: the routed experts' tiles hold e4m3fn bytes (pull_retile_kernel<uint8_t, false>); the shared expert stays bf16
   g->slot_f8 = slot_f8 && host_f8;
-  g->slot_dt = g->slot_f8 ? DT_F8 : g->dt;
+  g->slot_dt = g->slot_f8 ? DT_F8 : (g->slot_mx4 ? DT_MX4 : g->dt);  // (MXFP4 slots: the shared expert stays bf16, too)
   g->dlay = make_dev_layout(cfg->expert_type, g->H, g->F, g->slot_dt, g->slot_f8 ? 1 : g->es);
   if (g->has_shared) g->dlay_sh = make_dev_layout(cfg->expert_type, g->H, g->Fs, g->dt, g->es);
   g->slot_bytes = g->dlay.total;
@@ -436,6 +465,7 @@ static int create_engine(const moeinf_config* cfg, bool slot_f8, moeinf_engine**
       for (int i = 0; i < g->dlay.n; ++i) ok16 = ok16 && (g->dlay.K[i] > 0 ? g->dlay.K[i] % 16 == 0 : g->dlay.size[i] % 32 == 0);
       if (!ok16) { fail(MOEINF_ERR_UNSUPPORTED, "fp8 experts (dtype 3): hidden / inter (and bias lengths) must be multiples of 16"); return bail(MOEINF_ERR_UNSUPPORTED); }
     }
+    if (g->slot_mx4 && !g->h2d_pull) { fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are filled by the PULL tier mover: not with MOEINF_H2D_PULL=0"); return bail(MOEINF_ERR_UNSUPPORTED); }
     if (g->host_f8 && !g->h2d_pull) { fail(MOEINF_ERR_UNSUPPORTED, "fp8 experts (dtype 3) are up-cast by the PULL tier mover: not with MOEINF_H2D_PULL=0, nor with bias vectors that are not 16-byte multiples"); return bail(MOEINF_ERR_UNSUPPORTED); }
     if (g->h2d_pull) {
       TRYHIP(hipMalloc((void**)&g->d_copy_ts, (size_t)kCopyTsRing * 32));
@@ -1113,9 +1143,10 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   const int et = g->cfg.expert_type;
   const bool gated = (et == MOEINF_EXPERT_MIXTRAL || et == MOEINF_EXPERT_DEEPSEEK || et == MOEINF_EXPERT_SWITCH_GATED);
   const bool bias = (et == MOEINF_EXPERT_NLLB || et == MOEINF_EXPERT_FSGPT);
-  const int64_t wes = g->slot_f8 ? 1 : es;  // routed weight bytes per element (fp8 slots: 1)
-  const int64_t b1 = U * ((gated ? 2 : 1) * F * H * wes + (bias ? F * es : 0)) + (Tsh ? 2 * Fs * H * es : 0) + (rows + Tsh) * H * es + rows * F * es + Tsh * Fs * es;
-  const int64_t b2 = U * (H * F * wes + (bias ? H * es : 0)) + (Tsh ? H * Fs * es : 0) + rows * F * es + Tsh * Fs * es + (rows + Tsh) * H * es;
+  // bytes of one routed weight matrix in its slot's format (fp8 slots: 1 byte per weight; MXFP4 slots: codes and scales, 17/32)
+  const int64_t wm = g->slot_mx4 ? mx4_host_bytes(F, H) : F * H * (g->slot_f8 ? 1 : es);
+  const int64_t b1 = U * ((gated ? 2 : 1) * wm + (bias ? F * es : 0)) + (Tsh ? 2 * Fs * H * es : 0) + (rows + Tsh) * H * es + rows * F * es + Tsh * Fs * es;
+  const int64_t b2 = U * (wm + (bias ? H * es : 0)) + (Tsh ? H * Fs * es : 0) + rows * F * es + Tsh * Fs * es + (rows + Tsh) * H * es;
   g->prof.ffn1_bytes += b1;
   g->prof.ffn2_bytes += b2;
   if (local) {

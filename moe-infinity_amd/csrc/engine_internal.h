@@ -94,7 +94,9 @@ struct BlobLayout {
   int64_t off[4] = {0, 0, 0, 0}, size[4] = {0, 0, 0, 0};
   int64_t total = 0;
 };
-static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es) {
+// mx4: the routed experts of an MXFP4-slot engine — every matrix is ONE tensor, its packed e2m1 codes [R, K/2] followed by its e8m0
+// scales [R, K/32] (include/moeinf.h); gated families only (moeinf_create_ex refuses the others)
+static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es, bool mx4 = false) {
   BlobLayout b;
   auto add = [&](int64_t bytes) {
     b.off[b.n] = b.total;
@@ -106,6 +108,7 @@ static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es)
     case MOEINF_EXPERT_MIXTRAL:   // w1[F,H] w2[H,F] w3[F,H]
     case MOEINF_EXPERT_DEEPSEEK:  // gate[F,H] up[F,H] down[H,F]
     case MOEINF_EXPERT_SWITCH_GATED:  // wi_0[F,H] wi_1[F,H] wo[H,F] (expert_module.cpp:46-52)
+      if (mx4) { add(mx4_host_bytes(F, H)); add(mx4_host_bytes(F, H)); add(mx4_host_bytes(F, H)); break; }  // (= mx4_host_bytes(H, F))
       add(F * H * es); add(F * H * es); add(F * H * es);
       break;
     case MOEINF_EXPERT_NLLB:
@@ -121,7 +124,8 @@ static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es)
 }
 
 // Device-side (HBM slot) layout: matrices in MFMA-tile order (kernels.hip), biases raw; 4 KiB aligned.  dt / es: the SLOT's
-// element (DT_F8 / 1 for fp8 slots: 64 k per 1-KiB tile, half of bf16's bytes)
+// element (DT_F8 / 1 for fp8 slots: 64 k per 1-KiB tile, half of bf16's bytes; DT_MX4 for MXFP4 slots: 128 k per 1-KiB code tile and
+// the matrix's scale dwords behind its code tiles, kernels.h tiled_bytes)
 struct DevLayout {
   int n = 0;
   int64_t off[4] = {0, 0, 0, 0}, size[4] = {0, 0, 0, 0};
@@ -233,8 +237,9 @@ struct moeinf_engine {
   int num_cus = 0;                     // of THIS engine's device
   int layer1_switch_wgs_per_cu = -1;   // occupancy of the one-launch Switch kernel (asked once per engine)
   bool host_f8 = false;                // dtype id 3: fp8 (e4m3fn) experts in the host tier, bf16 slots and arithmetic
+  bool slot_mx4 = false;               // MXFP4 slots (moeinf_create_ex, MOEINF_SLOT_MXFP4): a bf16 engine whose routed experts are MXFP4 in the host tier AND in HBM
   bool slot_f8 = false;                // ... and fp8 slots (moeinf_create_ex): routed experts stay e4m3fn in HBM, bf16 arithmetic
-  int slot_dt = DT_BF16;               // dtype of the routed experts' slots (DT_F8 with slot_f8, else dt)
+  int slot_dt = DT_BF16;               // dtype of the routed experts' slots (DT_F8 with slot_f8, DT_MX4 with slot_mx4, else dt)
   int64_t host_es = 2;                 // bytes per element of the HOST blob (1 with host_f8, else es)
   bool route_v3 = false;               // MOEINF_ROUTER_DEEPSEEK_V3: cfg.router_kind is stored as DEEPSEEK
   std::vector<const float*> gate_bias; // ... per layer: e_score_correction_bias (borrowed device pointers)

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(NW * 64) void ffn_ep_kernel(FfnStage s, EpOwnArgs o
 }
 
 hipError_t launch_ffn_ep_stage(const FfnStage& s, const EpOwnArgs& o, hipStream_t st) {
-  if (s.wdtype == DT_F8) return hipErrorInvalidValue;  // fp8 slots are not built for expert parallelism (moeinf_create_ex refuses it)
+  if (s.wdtype == DT_F8 || s.wdtype == DT_MX4) return hipErrorInvalidValue;  // fp8 / MXFP4 slots are not built for expert parallelism (moeinf_create_ex refuses it)
   const dim3 grid((s.R + 15) / 16 + ((o.stage == 1 && o.mirror) ? 1 : 0), o.max_active);
   const bool gated = (s.epi == EPI_GATED_SILU || s.epi == EPI_GATED_GELU);
   const size_t kbytes = (size_t)s.K * dt_bytes(s.dtype);
@@ -482,7 +482,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(96))) void 
 
 hipError_t launch_ffn_epb_stage1(const RouteArgs& r, const FfnStage& s1, const FfnStage* sh2, const EpBcastArgs& b, EpOwnArgs::Rec* rec,
                                  int max_active, int with_bcast, hipStream_t st) {
-  if (s1.wdtype == DT_F8) return hipErrorInvalidValue;  // fp8 slots: not for expert parallelism
+  if (s1.wdtype == DT_F8 || s1.wdtype == DT_MX4) return hipErrorInvalidValue;  // fp8 / MXFP4 slots: not for expert parallelism
   const int n_rg = (s1.R + 15) / 16;
   const int n_sh2 = sh2 ? (sh2->R_sh + 15) / 16 : 0;
   const dim3 grid(1 + n_sh2 + max_active * n_rg + (b.mirror ? 1 : 0));

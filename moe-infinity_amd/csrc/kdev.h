@@ -332,6 +332,30 @@ __device__ __forceinline__ void f8x16_to_bf16(const u32x4 w, u32x4& lo, u32x4& h
 #undef CVT
 }
 
+// ---- MXFP4 weights (MXFP4 slots, moeinf_create_ex with MOEINF_SLOT_MXFP4): OCP e2m1 codes + one e8m0 scale per 32 k ---------------
+// Weight-element tag like f8w_t: activations stay bf16.  A code tile is 16 rows x 128 k in 1 KiB, lane l's 16 bytes = row l & 15,
+// k 32(l >> 4) .. +31 = exactly ONE MX block, so one scale per lane and tile.  The scales of a matrix follow its code tiles:
+// [four tiles][lane] dwords over the matrix's tiles in storage order (row group by row group), byte j of lane l's dword d = the
+// scale of row l & 15, block (l >> 4) of tile 4d + j (what pull_retile_mx4_kernel writes) — a lane fetches the scales of four
+// consecutive k-tiles with one 4-byte load, and the scales take exactly R * K / 32 bytes (rounded up to one dword per lane).
+struct mx4w_t {};
+template <> struct act_of<mx4w_t> { using type = uint16_t; };
+// 32 e2m1 codes (16 bytes, element 2j in the low nibble of byte j) x 2^(b - 127) -> four bf16x8 MFMA fragments (k 0..7, 8..15, 16..23,
+// 24..31 of the lane's thirty-two): v_cvt_scalef32_pk_bf16_fp4 up-casts two elements per instruction with the scale applied by the
+// hardware, exactly (e2m1 x 2^n has two significant bits and fits bf16's exponent range).  b: the e8m0 byte (0 and 255 are outside
+// the contract).
+__device__ __forceinline__ void mx4x32_to_bf16(const u32x4 w, const uint32_t b, u32x4 (&o)[4]) {
+  const float sc = __uint_as_float(b << 23);
+#define CVT(word, sel) __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((word), sc, (sel)))
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = u32x4{CVT(w[j], 0), CVT(w[j], 1), CVT(w[j], 2), CVT(w[j], 3)};
+#undef CVT
+}
+// a scale dword, through the global address space like the codes
+__device__ __forceinline__ uint32_t ld4_global(const void* p) {
+  return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(reinterpret_cast<uintptr_t>(p));
+}
+
 // ------------------------------------------------------------------------------------------------
 // ffn_rows: grouped expert FFN, one stage.  grid = (ceil(Rmax/16), n_active), block = NW waves.
 //
@@ -479,7 +503,12 @@ __device__ __forceinline__ void ffn_rows_item(const FfnStage& s, const int bx, c
                                               const bool to_peers = false) {
   constexpr bool F8W = std::is_same<WT, f8w_t>::value;
   static_assert(!F8W || std::is_same<T, uint16_t>::value, "fp8 weights run against bf16 activations");
-  constexpr int EPV = F8W ? 16 : DT<T>::EPV;  // weight elements per lane and tile
+  // MXFP4 slots: one 16-byte code load per lane and matrix per 128-k tile + the lane's scale byte, up-cast to four bf16 fragments, four
+  // MFMAs against the lane's 64 contiguous activation bytes at k 32q .. 32q+31.  K % 128 == 0 (moeinf_create_ex checks).  A wave takes
+  // U CONSECUTIVE k-tiles per batch (not every NW-th): with U % 4 == 0 they are whole scale dwords, one 4-byte load per four tiles.
+  constexpr bool MX4 = std::is_same<WT, mx4w_t>::value;
+  static_assert(!MX4 || std::is_same<T, uint16_t>::value, "MXFP4 weights run against bf16 activations");
+  constexpr int EPV = MX4 ? 32 : (F8W ? 16 : DT<T>::EPV);  // weight elements per lane and tile
   constexpr int EPT = 4 * EPV;  // k elements per tile (64 bytes per row)
   const int K = sh ? s.K_sh : s.K;
   const int R = sh ? s.R_sh : s.R;
@@ -523,6 +552,80 @@ __device__ __forceinline__ void ffn_rows_item(const FfnStage& s, const int bx, c
     // shorter batch is predicated (wave-uniform), not peeled into one-tile round trips (DeepSeek stage 2, 11 tiles per
     // wave: 3 round trips instead of 5, 13.7 -> 11.8 us per launch; issuing the first weight batch ahead of the
     // row_map round was measured too and bought nothing)
+    if constexpr (MX4) {
+      // scale dword d of a lane = the matrix's tiles 4d .. 4d+3, tiles numbered row group by row group (bx * KB + k-tile)
+      const int ntiles = ((R + 15) / 16) * KB, nwords = (ntiles + 3) / 4;
+      const size_t sc_off = (size_t)ntiles * 1024 + lane * 4;  // behind the matrix's code tiles
+      const char* s0 = W + s.off_a + sc_off;
+      const char* s1 = NMAT == 2 ? W + s.off_b + sc_off : nullptr;
+      // (sixteen waves per workgroup leave 128 VGPRs: with four tiles per batch — 64 activation, 32 code and 32 fragment registers —
+      // the gated stage compiled to 35 scratch instructions, with two to none; a compile-time finding, the form's speed is unmeasured)
+      constexpr int UX = (NMAT == 2 && NW == 16 && U > 2) ? 2 : U;
+      constexpr int SW = UX % 4 == 0 ? UX / 4 : UX;  // scale dwords per batch: one per four tiles, or (UX < 4) one per tile, re-read
+      for (int kb = wave * UX; kb < KBfull; kb += UX * NW) {  // kb: this wave's first tile of the batch
+        u32x4 av[UX], bv[UX], xq[UX][NT][4];
+        uint32_t sa[SW], sb[SW];
+        const int ft = bx * KB + kb;  // (wave-uniform)
+        if constexpr (UX % 4 == 0) {
+          // four tiles per dword; a row group that does not start on a dword (KB % 4 != 0) takes one dword more, shifted in
+          uint32_t wa[SW + 1], wb[SW + 1];
+#pragma unroll
+          for (int j = 0; j <= SW; ++j) {
+            wa[j] = 0u; wb[j] = 0u;
+            if ((j < SW || (ft & 3)) && (ft >> 2) + j < nwords && kb - (ft & 3) + 4 * j < KBfull) {
+              wa[j] = ld4_global(s0 + (size_t)((ft >> 2) + j) * 256);
+              if (NMAT == 2) wb[j] = ld4_global(s1 + (size_t)((ft >> 2) + j) * 256);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < SW; ++j) {
+            sa[j] = __builtin_amdgcn_alignbyte(wa[j + 1], wa[j], (uint32_t)(ft & 3));
+            if (NMAT == 2) sb[j] = __builtin_amdgcn_alignbyte(wb[j + 1], wb[j], (uint32_t)(ft & 3));
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < SW; ++j) {
+            if (kb + j < KBfull) {
+              sa[j] = ld4_global(s0 + (size_t)((ft + j) >> 2) * 256);
+              if (NMAT == 2) sb[j] = ld4_global(s1 + (size_t)((ft + j) >> 2) * 256);
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < UX; ++i) {
+          if (kb + i < KBfull) {
+            av[i] = ld16_nt_global(a0 + (size_t)(kb + i) * 1024);
+            if (NMAT == 2) bv[i] = ld16_nt_global(a1 + (size_t)(kb + i) * 1024);
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt)
+              if (tt < ntl) {
+                const T* xp = xr[tt] + (size_t)(kb + i) * EPT;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) xq[i][tt][c] = COHI ? ld16_coherent(xp + 8 * c) : ld16(xp + 8 * c);
+              }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < UX; ++i) {
+          if (kb + i < KBfull) {
+            const int sj = UX % 4 == 0 ? i >> 2 : i, sh8 = UX % 4 == 0 ? (i & 3) * 8 : ((ft + i) & 3) * 8;
+            u32x4 fa[4], fb[4];
+            mx4x32_to_bf16(av[i], (sa[sj] >> sh8) & 255u, fa);
+            if (NMAT == 2) mx4x32_to_bf16(bv[i], (sb[sj] >> sh8) & 255u, fb);
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) {
+              if (tt < ntl) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                  mma16<T>(acc0[tt], fa[c], xq[i][tt][c]);
+                  if (NMAT == 2) mma16<T>(acc1[tt], fb[c], xq[i][tt][c]);
+                }
+              }
+            }
+          }
+        }
+      }
+    } else
     for (int kb = wave; kb < KBfull; kb += U * NW) {
       u32x4 av[U], bv[U], xv[U][NT], xw[F8W ? U : 1][F8W ? NT : 1];  // xw: the second 16 activation bytes of an fp8 tile
 #pragma unroll
@@ -570,7 +673,7 @@ __device__ __forceinline__ void ffn_rows_item(const FfnStage& s, const int bx, c
         }
       }
     }
-    if (!F8W && KB != KBfull && wave == (KBfull % NW)) {  // zero-padded last tile: guard only the activation read
+    if (!F8W && !MX4 && KB != KBfull && wave == (KBfull % NW)) {  // zero-padded last tile: guard only the activation read
       const u32x4 z = {0u, 0u, 0u, 0u};
       const u32x4 w0 = ld16_nt(a0 + (size_t)KBfull * 1024);
       u32x4 w1 = w0;

@@ -12,7 +12,12 @@ enum { DT_BF16 = 0, DT_F32 = 1, DT_F16 = 2 };  // = the reference's dtype ids (c
 // fp8 (OCP e4m3fn) as the dtype of an HBM SLOT only (fp8 slots, moeinf_create_ex): the weights of routed experts; activations and
 // arithmetic stay bf16.  Never a stage's (activation) dtype.
 constexpr int DT_F8 = 3;
+// OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 k of a row) as the dtype of an HBM SLOT only (MXFP4 slots, moeinf_create_ex with
+// MOEINF_SLOT_MXFP4): like DT_F8 the weights of routed experts; activations and arithmetic stay bf16.  Not a dtype id of the C ABI.
+constexpr int DT_MX4 = 4;
 inline int dt_bytes(int dtype) { return dtype == DT_F32 ? 4 : (dtype == DT_F8 ? 1 : 2); }
+// bytes of an [R, K] matrix in its MXFP4 HOST tensor: the packed codes [R, K/2], then the scales [R, K/32]
+inline int64_t mx4_host_bytes(int64_t R, int64_t K) { return R * (K / 2) + R * (K / 32); }
 struct EpFuse;
 
 // ---- direct peer-store exchange (expert parallelism without a collective; host side: ep_peer.h) ------------------
@@ -204,6 +209,7 @@ inline Ring2Form ring2_form(bool f16, int nmat, int K, int K_sh, int row_groups,
 struct FfnShape {
   int dtype = DT_BF16;       // activation dtype: DT_BF16, DT_F16, anything else runs as fp32
   bool f8w = false;          // the routed experts' weights are an fp8 slot (FfnStage::wdtype == DT_F8)
+  bool mx4w = false;         // ... an MXFP4 slot (FfnStage::wdtype == DT_MX4)
   int nmat = 1;              // 2: gated stage, 1: plain
   int epi = EPI_NONE;
   int K = 0, K_sh = 0;       // reduction lengths of the routed / shared experts (K_sh = 0: no shared expert in the launch)
@@ -226,6 +232,10 @@ inline FfnShape ffn_shape(const FfnStage& s) {
   h.rows_fit = !(s.rows_bound > 0 && s.rows_bound * s.ld_in >= (int64_t(1) << 32));
   h.fuse_combine = s.fuse_combine != 0;
   h.row_bytes = (int64_t)(s.K > s.K_sh ? s.K : s.K_sh) * (h.f8w ? 1 : dt_bytes(s.dtype));
+  if (s.wdtype == DT_MX4) {  // (the longer of the routed expert's code row and the bf16 shared expert's row)
+    h.mx4w = true;
+    h.row_bytes = s.K / 2 > (int64_t)s.K_sh * dt_bytes(s.dtype) ? s.K / 2 : (int64_t)s.K_sh * dt_bytes(s.dtype);
+  }
   return h;
 }
 
@@ -251,6 +261,8 @@ inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus
   f.nmat = s.nmat;
   // fp8 slots: bf16 activations, whole fp8 tiles, and only the gated-SiLU and plain no-epilogue stages (Mixtral / DeepSeek)
   if (s.f8w && (s.dtype != DT_BF16 || s.K % 64 != 0 || (s.epi != EPI_GATED_SILU && s.epi != EPI_NONE))) { f.kernel = FFN_NONE; return f; }
+  // MXFP4 slots: the same stages on whole 128-k code tiles
+  if (s.mx4w && (s.dtype != DT_BF16 || s.K % 128 != 0 || (s.epi != EPI_GATED_SILU && s.epi != EPI_NONE))) { f.kernel = FFN_NONE; return f; }
   // the row kernel: long reductions get 8 waves per workgroup (more bytes in flight per CU), short ones 4 ... and a grid of at most
   // one workgroup per CU (Switch-base-8 at batch 1: 192 / 48 workgroups for 256 CUs) SIXTEEN: a CU that owns a single work item has
   // nothing else to hide its load latency behind, so the whole item goes in flight at once (round 4: stage 2 of Switch-base-8
@@ -272,6 +284,8 @@ inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus
   f.waves = nw == 8 ? 8 : 4;
   // the grouped GEMMs are built for the SiLU gate only: the gelu gate runs the row kernel at every size
   if (s.epi == EPI_GATED_GELU) return f;
+  // ... and so does an MXFP4 slot: MX4 forms of the grouped GEMMs are not built
+  if (s.mx4w) return f;
   const int ept = (s.dtype == DT_BF16 || s.dtype == DT_F16) ? 32 : 16;  // activation elements per 64-byte k-tile
   const bool k_ok = s.K % ept == 0 && s.K_sh % ept == 0;
   int use_gemm = k.use_gemm;
@@ -357,7 +371,12 @@ hipError_t launch_retile_blob(const RetileBlob& b, int dtype, hipStream_t st);
 // the same from PINNED HOST memory (b.src = device-visible host pointer): the tier mover's pull form, `workgroups` x 256 threads
 // ts: nullptr, or a 4 x u64 timing record in device memory {start tick of the copy's first launch (written when first != 0), max end tick, finished workgroups, -}
 hipError_t launch_pull_retile(const RetileBlob& b, int dtype, int workgroups, hipStream_t st, unsigned long long* ts = nullptr, int first = 1);
-inline int64_t tiled_bytes(int64_t R, int64_t K, int dtype) { const int64_t ept = dtype == DT_F32 ? 16 : (dtype == DT_F8 ? 64 : 32); return ((R + 15) / 16) * ((K + ept - 1) / ept) * 1024; }
+inline int64_t tiled_bytes(int64_t R, int64_t K, int dtype) {
+  // an MXFP4 slot: code tiles of 16 rows x 128 k (K % 128 == 0), then one scale dword per lane and FOUR consecutive tiles (kdev.h)
+  if (dtype == DT_MX4) { const int64_t tiles = ((R + 15) / 16) * (K / 128); return tiles * 1024 + ((tiles + 3) / 4) * 256; }
+  const int64_t ept = dtype == DT_F32 ? 16 : (dtype == DT_F8 ? 64 : 32);
+  return ((R + 15) / 16) * ((K + ept - 1) / ept) * 1024;
+}
 
 struct RouteArgs {
   const void* x;        // [T,H] dtype x_dtype

@@ -226,8 +226,131 @@ __global__ __launch_bounds__(256) void pull_retile_kernel(RetileBlob b, unsigned
     atomicAdd(&ts[2], 1ull);
   }
 }
+// The pull form for an MXFP4 slot (kdev.h: mx4w_t).  Tensor t of the host blob = the packed codes [R, K/2] bytes, then the scales
+// [R, K/32] bytes (b.K[t] = K, the logical reduction length).  The codes take pull_retile_kernel<uint8_t, false>'s path over K/2
+// "elements" (a 1-KiB unit of a source row = 2048 k = sixteen code tiles).  The scales of G row groups are one CONTIGUOUS piece of
+// the source (16 rows x K/32 bytes each, rows in order) and of the slot (K/128 tiles x 64 lanes), so a scale unit is up to 16 KiB
+// pulled with the same four 16-byte loads per lane and re-ordered through LDS into the [four tiles][lane] dwords the kernels load.
+// G: the fewest row groups whose tiles are whole dwords, times what fits 16 KiB (mx4_scale_groups; the engine refuses longer rows).
+__host__ __device__ inline int mx4_scale_groups(int K) {
+  const int KB = K / 128, ga = (KB % 4 == 0) ? 1 : ((KB % 2 == 0) ? 2 : 4);
+  const int fit = 16384 / (KB * 64) / ga * ga;
+  return fit > ga ? fit : ga;
+}
+__global__ __launch_bounds__(256) void pull_retile_mx4_kernel(RetileBlob b, unsigned long long* ts, int first) {
+  if (ts && first && blockIdx.x == 0 && threadIdx.x == 0) ts[0] = (unsigned long long)wall_clock64();
+  constexpr int LROW = 1024 + 16;
+  __shared__ __attribute__((aligned(16))) char lds[16 * LROW];  // codes: sixteen padded rows; scales: 16 KiB flat
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int ncode[4], kcs[4], nsc[4], total = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const bool on = t < b.n;
+    const int K2 = on ? b.K[t] / 2 : 0, RG = on ? (b.R[t] + 15) / 16 : 0;
+    kcs[t] = on ? (K2 + 1023) / 1024 : 1;
+    ncode[t] = RG * kcs[t];
+    const int G = on ? mx4_scale_groups(b.K[t]) : 1;
+    nsc[t] = (RG + G - 1) / G;
+    total += ncode[t] + nsc[t];
+  }
+  u32x4 raw[4];
+  uint32_t okmask = 0;
+  // unit i -> tensor t, scales or codes, and its index inside that part (a tensor's code units, then its scale units)
+  auto decode = [&](int i, int& t, bool& sc, int& ui) {
+    t = 0;
+    while (t < 3 && i >= ncode[t] + nsc[t]) { i -= ncode[t] + nsc[t]; ++t; }
+    sc = i >= ncode[t];
+    ui = sc ? i - ncode[t] : i;
+  };
+  auto load = [&](int i) {
+    int t, ui; bool sc;
+    decode(i, t, sc, ui);
+    const char* src = reinterpret_cast<const char*>(b.src) + b.src_off[t];
+    const int K2 = b.K[t] / 2, R = b.R[t];
+    const int KS = b.K[t] / 32, G = mx4_scale_groups(b.K[t]);
+    const int rg = sc ? 0 : ui / kcs[t], kc = sc ? 0 : ui - rg * kcs[t];
+    const size_t sc_total = (size_t)R * KS, sc_base = (size_t)ui * G * 16 * KS;  // bytes of the tensor's scales, first byte of this unit
+    const size_t sc_len = min((size_t)G * 16 * KS, sc_total - min(sc_total, sc_base));
+    okmask = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      size_t off;
+      bool ok;
+      if (!sc) {
+        const int row = rg * 16 + wave * 4 + j, k = kc * 1024 + lane * 16;  // (K/2 % 16 == 0: K % 128 == 0)
+        ok = row < R && k < K2;
+        off = (size_t)min(row, R - 1) * K2 + min(k, K2 - 16);
+      } else {
+        const size_t o = (size_t)(j * 256 + threadIdx.x) * 16;  // (scale bytes of a tensor are a multiple of 64)
+        ok = o < sc_len;
+        off = (size_t)R * K2 + min(sc_base + o, sc_total - 16);
+      }
+      raw[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + off));
+      okmask |= (ok ? 1u : 0u) << j;
+    }
+  };
+  int i = blockIdx.x;
+  if (i < total) load(i);
+  for (; i < total; i += gridDim.x) {
+    int t, ui; bool sc;
+    decode(i, t, sc, ui);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      u32x4 o = raw[j];
+      if (!((okmask >> j) & 1u)) o = u32x4{0u, 0u, 0u, 0u};
+      if (!sc) *reinterpret_cast<u32x4*>(lds + (wave * 4 + j) * LROW + lane * 16) = o;
+      else *reinterpret_cast<u32x4*>(lds + (size_t)(j * 256 + threadIdx.x) * 16) = o;
+    }
+    __syncthreads();
+    if (i + (int)gridDim.x < total) load(i + gridDim.x);  // in flight while this unit leaves through LDS
+    const int KB = b.K[t] / 128, RG = (b.R[t] + 15) / 16;
+    char* dst = reinterpret_cast<char*>(b.dst) + b.dst_off[t];
+    if (!sc) {
+      const int rg = ui / kcs[t], kc = ui - rg * kcs[t];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int kbl = wave * 4 + j, kb = kc * 16 + kbl;  // tile of this unit: row lane & 15, 16-byte piece lane >> 4
+        if (kb < KB) {
+          const u32x4 w4 = *reinterpret_cast<const u32x4*>(lds + (lane & 15) * LROW + kbl * 64 + (lane >> 4) * 16);
+          *reinterpret_cast<u32x4*>(dst + ((size_t)rg * KB + kb) * 1024 + lane * 16) = w4;
+        }
+      }
+    } else {
+      const int G = mx4_scale_groups(b.K[t]), KS = KB * 4;
+      const int rg0 = ui * G, ng = min(G, RG - rg0);
+      const int nt = ng * KB, ndw = (nt + 3) / 4;  // tiles of this unit, dwords per lane ((rg0 * KB) % 4 == 0 by the choice of G)
+      char* sdst = dst + (size_t)RG * KB * 1024 + (size_t)(rg0 * KB / 4) * 256;
+      for (int idx = threadIdx.x; idx < ndw * 64; idx += 256) {
+        const int d = idx >> 6, l = idx & 63;
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int f = 4 * d + j;
+          if (f < nt) {
+            const int rgl = f / KB, kb = f - rgl * KB;
+            w |= (uint32_t)(uint8_t)lds[rgl * 16 * KS + (l & 15) * KS + kb * 4 + (l >> 4)] << (8 * j);
+          }
+        }
+        *reinterpret_cast<uint32_t*>(sdst + (size_t)idx * 4) = w;
+      }
+    }
+    __syncthreads();
+  }
+  if (ts && threadIdx.x == 0) {
+    atomicMax(&ts[1], (unsigned long long)wall_clock64());
+    __threadfence();
+    atomicAdd(&ts[2], 1ull);
+  }
+}
 hipError_t launch_pull_retile(const RetileBlob& b, int dtype, int workgroups, hipStream_t st, unsigned long long* ts, int first) {
   const dim3 grid(workgroups < 1 ? 1 : workgroups);
+  if (dtype == DT_MX4) {  // MXFP4 slot: codes + scales of the host blob -> code tiles + scale dwords
+    if (b.src_f8) return hipErrorInvalidValue;
+    for (int t = 0; t < b.n; ++t)
+      if (b.K[t] <= 0 || b.K[t] % 128 || b.R[t] % 16 || mx4_scale_groups(b.K[t]) * (b.K[t] / 128) * 64 > 16384) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pull_retile_mx4_kernel, grid, dim3(256), 0, st, b, ts, first);
+    return hipGetLastError();
+  }
   if (dtype == DT_F8) {  // fp8 slot: fp8 host bytes -> fp8 tiles (16 rows x 64 k per KiB), nothing widened
     if (b.src_f8) return hipErrorInvalidValue;
     hipLaunchKernelGGL((pull_retile_kernel<uint8_t, false>), grid, dim3(256), 0, st, b, ts, first);
@@ -313,6 +436,7 @@ hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_
     case FFN_NONE: return hipErrorInvalidValue;
     case FFN_ROWS:
       if (h.f8w) { if (gated) launch_ffn_rows<f8w_t, 2>(s, grid, f, st); else launch_ffn_rows<f8w_t, 1>(s, grid, f, st); }
+      else if (h.mx4w) { if (gated) launch_ffn_rows<mx4w_t, 2>(s, grid, f, st); else launch_ffn_rows<mx4w_t, 1>(s, grid, f, st); }
       else if (s.dtype == DT_BF16) { if (gated) launch_ffn_rows<uint16_t, 2>(s, grid, f, st); else launch_ffn_rows<uint16_t, 1>(s, grid, f, st); }
       else if (s.dtype == DT_F16) { if (gated) launch_ffn_rows<half_t, 2>(s, grid, f, st); else launch_ffn_rows<half_t, 1>(s, grid, f, st); }
       else { if (gated) launch_ffn_rows<float, 2>(s, grid, f, st); else launch_ffn_rows<float, 1>(s, grid, f, st); }
@@ -775,6 +899,12 @@ hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const F
     else KL((ffn1_selfroute_kernel<f8w_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
     return hipGetLastError();
   }
+  if (s1.wdtype == DT_MX4) {  // MXFP4 slots (gated families, bf16)
+    if (s1.epi != EPI_GATED_SILU || s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
+    if (sr_u == 8) KL((ffn1_selfroute_kernel<mx4w_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+    else KL((ffn1_selfroute_kernel<mx4w_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+    return hipGetLastError();
+  }
   if (s1.epi != EPI_GATED_SILU) {
     // plain experts (Switch, top-1): a grid of at most one workgroup per CU gets sixteen waves per workgroup — the whole
     // work item in flight at once (see launch_ffn_stage)
@@ -887,6 +1017,10 @@ hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, c
     if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
     if (grid.x > 4 * 256) SRM(f8w_t, 4); else SRM(f8w_t, 8);
   }
+  else if (s1.wdtype == DT_MX4) {  // MXFP4 slots (bf16)
+    if (s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
+    if (grid.x > 4 * 256) SRM(mx4w_t, 4); else SRM(mx4w_t, 8);
+  }
   else if (s1.dtype == DT_F16) { if (grid.x > 4 * 256) SRM(half_t, 4); else SRM(half_t, 8); }
   else { if (grid.x > 4 * 256) SRM(uint16_t, 4); else SRM(uint16_t, 8); }
 #undef SRM
@@ -946,7 +1080,8 @@ template <typename T, int NWE, int U>  // T: uint16_t = bf16, half_t = fp16 (rou
 __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStage s) {
   using A = typename act_of<T>::type;
   constexpr bool F8W = std::is_same<T, f8w_t>::value;
-  constexpr int EPT = F8W ? 64 : 32, EPV = F8W ? 16 : 8;
+  constexpr bool MX4 = std::is_same<T, mx4w_t>::value;  // MXFP4 slots: 128-k code tiles, ffn_rows_item's MXFP4 form; K % 128 == 0
+  constexpr int EPT = MX4 ? 128 : (F8W ? 64 : 32), EPV = MX4 ? 32 : (F8W ? 16 : 8);
   __shared__ float red[2][NWE][16];
   __shared__ float yv[2][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -963,7 +1098,39 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
   const char* a0 = W + s.off_a + (size_t)rg * KB * 1024 + lane * 16;
   const A* xr = reinterpret_cast<const A*>(s.in) + (size_t)g * s.ld_in + q * EPV;  // T == 1: h row of slot g
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (F8W) {
+  if constexpr (MX4) {
+    static_assert(U % 4 == 0, "whole scale dwords per batch");
+    const int ntiles = ((s.R + 15) / 16) * KB, nwords = (ntiles + 3) / 4;
+    const char* s0 = W + s.off_a + (size_t)ntiles * 1024 + lane * 4;
+    for (int kb = wl * U; kb < KB; kb += U * NWE) {  // U consecutive tiles per wave and batch, as ffn_rows_item's MXFP4 form
+      u32x4 av[U], xq[U][4];
+      uint32_t wa[U / 4 + 1];
+      const int ft = rg * KB + kb;
+#pragma unroll
+      for (int j = 0; j <= U / 4; ++j) {
+        wa[j] = 0u;
+        if ((j < U / 4 || (ft & 3)) && (ft >> 2) + j < nwords && kb - (ft & 3) + 4 * j < KB) wa[j] = ld4_global(s0 + (size_t)((ft >> 2) + j) * 256);
+      }
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        if (kb + i < KB) {
+          av[i] = ld16_nt_global(a0 + (size_t)(kb + i) * 1024);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) xq[i][c] = ld16(xr + (size_t)(kb + i) * EPT + 8 * c);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        if (kb + i < KB) {
+          const uint32_t sw = __builtin_amdgcn_alignbyte(wa[i / 4 + 1], wa[i / 4], (uint32_t)(ft & 3));
+          u32x4 fa[4];
+          mx4x32_to_bf16(av[i], (sw >> ((i & 3) * 8)) & 255u, fa);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) mma16<A>(acc, fa[c], xq[i][c]);
+        }
+      }
+    }
+  } else if constexpr (F8W) {
     for (int kb = wl; kb < KB; kb += U * NWE) {
       u32x4 av[U], xv[U], xw[U];
 #pragma unroll
@@ -1043,6 +1210,22 @@ hipError_t launch_ffn2_decode1(const FfnStage& s2, hipStream_t st) {
     if ((size_t)s2.K >= 16384) KL((ffn2_decode1_kernel<f8w_t, 8, 4>), grid, dim3(512), 0, st, s2);  // (as bf16: by weight bytes per row)
     else if (du == 8) KL((ffn2_decode1_kernel<f8w_t, 4, 8>), grid, dim3(256), 0, st, s2);
     else KL((ffn2_decode1_kernel<f8w_t, 4, 4>), grid, dim3(256), 0, st, s2);
+    return hipGetLastError();
+  }
+  if (s2.wdtype == DT_MX4) {  // MXFP4 slots (gated families, bf16): the same two forms on MXFP4 tiles
+    if (s2.dtype != DT_BF16 || s2.comb.kind > 1 || (s2.K % 128) != 0) return hipErrorInvalidValue;
+    static const int pu = env_int("MOEINF_DEC1_PAIR_U", 4);
+    if (pair_env && s2.comb.K == 2 && !(s2.comb.kind == 1 && s2.comb.y_shared)) {
+      const dim3 g1((s2.R + 15) / 16);
+      if (pu == 8) KL((ffn2_decode1_pair_kernel<mx4w_t, 4, 8>), g1, dim3(512), 0, st, s2);
+      else KL((ffn2_decode1_pair_kernel<mx4w_t, 4, 4>), g1, dim3(512), 0, st, s2);
+      return hipGetLastError();
+    }
+    const dim3 grid((s2.R + 15) / 16, s2.comb.K);
+    static const int du = env_int("MOEINF_DEC1_U", 4);
+    if ((size_t)s2.K >= 32768) KL((ffn2_decode1_kernel<mx4w_t, 8, 4>), grid, dim3(512), 0, st, s2);  // (as bf16: by weight bytes per row)
+    else if (du == 8) KL((ffn2_decode1_kernel<mx4w_t, 4, 8>), grid, dim3(256), 0, st, s2);
+    else KL((ffn2_decode1_kernel<mx4w_t, 4, 4>), grid, dim3(256), 0, st, s2);
     return hipGetLastError();
   }
   if (pair_env && (s2.dtype == DT_BF16 || s2.dtype == DT_F16) && s2.comb.K == 2 && (s2.K % 32) == 0 && !(s2.comb.kind == 1 && s2.comb.y_shared) && s2.comb.kind <= 1) {

@@ -225,6 +225,10 @@ hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnSt
     if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
     if (r.gate_dtype == DT_BF16) F1U(f8w_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(f8w_t, float); else return hipErrorInvalidValue;
   }
+  else if (s1.wdtype == DT_MX4) {  // MXFP4 slots (bf16)
+    if (s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
+    if (r.gate_dtype == DT_BF16) F1U(mx4w_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(mx4w_t, float); else return hipErrorInvalidValue;
+  }
   else if (s1.dtype == DT_BF16) { if (r.gate_dtype == DT_BF16) F1U(uint16_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(uint16_t, float); else return hipErrorInvalidValue; }
   else if (s1.dtype == DT_F16) { if (r.gate_dtype == DT_F16) F1U(half_t, half_t); else if (r.gate_dtype == DT_F32) F1U(half_t, float); else return hipErrorInvalidValue; }
   else return hipErrorInvalidValue;
@@ -378,7 +382,7 @@ int layer1_switch_wgs_per_cu(int x_dtype, int gate_dtype) {
 }
 
 bool launch_moe_layer1_switch(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage& s2, const LayerSync& sy, int num_cus, int wgs_per_cu, hipStream_t st) {
-  if (s1.wdtype == DT_F8 || s2.wdtype == DT_F8) return false;  // (Switch experts never have fp8 slots: moeinf_create_ex refuses them)
+  if (s1.wdtype == DT_F8 || s2.wdtype == DT_F8 || s1.wdtype == DT_MX4 || s2.wdtype == DT_MX4) return false;  // (Switch experts never have fp8 or MXFP4 slots: moeinf_create_ex refuses them)
   constexpr int KS = 4, P2 = 6, NW = 8;
   const int n_rg = (s1.R + 15) / 16, n_col = (s2.R + 15) / 16;
   const dim3 grid(r.E + 1 + n_rg + KS * n_col);

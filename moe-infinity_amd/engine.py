@@ -63,10 +63,10 @@ class MoEEngine:
             if name == "norm_topk_prob":
                 v = int(bool(v))
             setattr(c, name, v)
-        if cfg.fp8_slots:
+        if cfg.fp8_slots or cfg.mxfp4_slots:
             opts = _lib.CreateOptions()
             opts.struct_bytes = C.sizeof(_lib.CreateOptions)
-            opts.slot_dtype = DTYPE_F8E4M3
+            opts.slot_dtype = _lib.SLOT_MXFP4 if cfg.mxfp4_slots else DTYPE_F8E4M3
             check(self.lib.moeinf_create_ex(C.byref(c), C.byref(opts), C.byref(self._h)))
         else:
             check(self.lib.moeinf_create(C.byref(c), C.byref(self._h)))
@@ -83,7 +83,8 @@ class MoEEngine:
 
     @property
     def slot_dtype(self) -> int:
-        """The dtype id (config.DTYPE_*) the HBM expert slots hold: DTYPE_F8E4M3 with fp8 slots; bf16 for the default fp8 engine."""
+        """The dtype id (config.DTYPE_*) the HBM expert slots hold: DTYPE_F8E4M3 with fp8 slots; bf16 for the default fp8 engine;
+        config.SLOT_MXFP4 with MXFP4 slots."""
         v = C.c_int32()
         check(self.lib.moeinf_slot_dtype(self._h, C.byref(v)))
         return v.value
@@ -111,11 +112,25 @@ class MoEEngine:
         return list(off)[: n.value], list(siz)[: n.value], tot.value
 
     def pack_expert(self, tensors: Sequence[torch.Tensor], which: int = 0) -> torch.Tensor:
-        """Tensors in the reference's blob order -> one 4 KiB-aligned uint8 blob (CPU)."""
+        """Tensors in the reference's blob order -> one 4 KiB-aligned uint8 blob (CPU).  The routed experts of an MXFP4-slot engine
+        (which = 0): a sequence of (codes uint8 [R, K/2], scales uint8 [R, K/32]) pairs, quant.mxfp4_quantize's output."""
         off, siz, tot = self.expert_layout(which)
         if len(tensors) != len(off):
             raise ValueError(f"expected {len(off)} tensors, got {len(tensors)}")
         blob = torch.zeros(tot, dtype=torch.uint8)
+        if self.cfg.mxfp4_slots and which == 0:
+            for pair, o, s in zip(tensors, off, siz):
+                if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                    raise ValueError("an MXFP4-slot engine takes (codes, scales) pairs (quant.mxfp4_quantize)")
+                codes, scales = (p.detach().to("cpu").contiguous() for p in pair)
+                if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2:
+                    raise ValueError("codes and scales must be 2-D uint8 tensors")
+                if codes.shape[0] != scales.shape[0] or codes.shape[1] != 16 * scales.shape[1] or codes.numel() + scales.numel() != s:
+                    raise ValueError(f"codes {tuple(codes.shape)} / scales {tuple(scales.shape)} where the layout needs {s} bytes "
+                                     "([R, K/2] codes followed by [R, K/32] scales)")
+                blob[o:o + codes.numel()] = codes.reshape(-1)
+                blob[o + codes.numel():o + s] = scales.reshape(-1)
+            return blob
         for t, o, s in zip(tensors, off, siz):
             t = t.detach().to("cpu", self.host_dtype).contiguous()
             if t.numel() * t.element_size() != s:
