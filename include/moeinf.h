@@ -169,6 +169,23 @@ int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int activ
  * 2 = ffn_gemm_lds, 3 = ffn_gemm_ring2 (their fp8-weight forms); out[1]: waves per workgroup (hyb, lds) or token groups per pass
  * (ring2); out[2..5]: ring2's split tail, row blocks per expert, first split unit, workgroups (as out[1..4] of moeinf_ffn_ring2_form). */
 int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out6);
+/* Which launches make up a forward, and which form each decode launcher takes: one function decides (csrc/kernels.h layer_form,
+ * DESIGN.md section 4.3).  shape[21], the fields of LayerShape in order: router kind (MOEINF_ROUTER_* as the engine keeps it:
+ * DEEPSEEK_V3 = DEEPSEEK with shape[13] set, SOFTMAX_TOPK = MIXTRAL), expert type, activation dtype, gate dtype, slot dtype
+ * (MOEINF_DTYPE_*, MOEINF_DTYPE_F8E4M3 or MOEINF_SLOT_MXFP4), tokens, top-k, experts, hidden, inter, shared inter, has a shared
+ * expert, n_group, V3 gate, Switch expert capacity, MOEINF_FWD_* flags, has a token mask, sync-free (1) or decision path (0),
+ * stage 2 writes to an override buffer, compute units, workgroups of the Switch one-launch kernel a CU holds.
+ * out[26]: [0] shared expert hidden under the router; [1] self-routing stage 1: 0 none, 1 batch 1, 2 a batch of 2..8; [2] the gate
+ * rides in stage 1's launch (front1); [3] Switch one-launch layer: 0 no, 1 yes, 2 chosen but the launcher does not take the shape
+ * (three launches); [4] router launches: 0 none, 1 gate, 2 gate + shared stage 1, 3 that and route + shared stage 2, 4 gate and
+ * route + index, 5 gate, top-k, index, 6 gate, top-k, wide index; [5] the gate launch: 0 none of its own, 1 / 4 tokens per
+ * workgroup, 16 the fp64-MFMA tiles; [6] stage 1: 0 none, 1 launch_ffn_stage (moeinf_ffn_form), 2 ffn1_selfroute, 3
+ * ffn1_selfroute_multi, 4 moe_front1, 5 the Switch one-launch layer; [7..11] its self-routing geometry: waves, tiles per batch,
+ * dynamic LDS in KB, shared expert dispatched last, workgroups; [12] stage 2: 0 none, 1 launch_ffn_stage, 6 ffn2_decode1;
+ * [13..17] ffn2_decode1's form: pair kernel, waves, unroll, grid x, grid y; [18..19] / [20..21] waves and unroll of the shared
+ * expert's stage in gate_shared1 / route_shared2; [22] stage 2 may fuse the combine; [23] its fuse mode; [24] stage 1 carries
+ * its own kernel timer; [25] sleep repetitions between two counter polls of a fused launch (stage 1 = 4 or 5, else 0). */
+int moeinf_layer_form(const int32_t* shape, int n_shape, int32_t* out, int n_out);
 /* The fence ring (csrc/engine_internal.h): sync-free forwards record a fence event only every MOEINF_FENCE_EVERY-th time; a copy
  * that recycles a slot waits for the OLDEST recorded fence that covers the slot's last reader.  moeinf_fence_ring: entries in the
  * ring; moeinf_fence_cover_pos: the ring position that lookup returns (-1: no recorded fence covers `forward` yet) for

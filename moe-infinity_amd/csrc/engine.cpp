@@ -93,6 +93,27 @@ extern "C" int moeinf_ffn_form(int dtype, int epi, int K, int K_sh, int R, int a
   return MOEINF_OK;
 }
 
+// layer_form for the 21 numbers of a LayerShape, in the order of its fields (include/moeinf.h); the knobs as the environment holds
+// them NOW
+extern "C" int moeinf_layer_form(const int32_t* shape, int n_shape, int32_t* out, int n_out) {
+  if (!shape || !out || n_shape != 21 || n_out != 26) return fail(MOEINF_ERR_INVALID, "moeinf_layer_form: 21 shape numbers in, 26 out");
+  moeinf::LayerShape s;
+  int* const dst[21] = {&s.router_kind, &s.expert_type, &s.dtype, &s.gate_dtype, &s.slot_dtype, &s.T, &s.K, &s.E, &s.H, &s.F, &s.Fs, &s.has_shared,
+                        &s.n_group, &s.v3, &s.capacity, &s.flags, &s.masked, &s.fast, &s.ovr_out, &s.num_cus, &s.l1_wgs_per_cu};
+  for (int i = 0; i < 21; ++i) *dst[i] = shape[i];
+  if (s.slot_dtype == MOEINF_DTYPE_F8E4M3) s.slot_dtype = moeinf::DT_F8;
+  else if (s.slot_dtype == MOEINF_SLOT_MXFP4) s.slot_dtype = moeinf::DT_MX4;
+  if (s.T <= 0 || s.K <= 0 || s.E <= 0 || s.H <= 0 || s.F <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_layer_form: bad shape");
+  const moeinf::LayerForm f = moeinf::layer_form(s, moeinf::LayerKnobs::from_env());
+  const int32_t v[26] = {f.hide_shared, f.selfroute, f.front1, f.layer1_switch, f.router, f.gate, f.stage1,
+                         f.sr.waves, f.sr.tiles, f.sr.lds_kb, f.sr.shared_last, f.sr.grid,
+                         f.stage2, f.dec1.pair, f.dec1.waves, f.dec1.unroll, f.dec1.grid_x, f.dec1.grid_y,
+                         f.shared1.waves, f.shared1.unroll, f.shared2.waves, f.shared2.unroll,
+                         f.can_fuse_combine, f.fuse_mode, f.kt1, f.poll_sleep};
+  memcpy(out, v, sizeof v);
+  return MOEINF_OK;
+}
+
 extern "C" int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out5) {
   if (!out5 || (nmat != 1 && nmat != 2) || K <= 0 || R <= 0 || active <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_ffn_ring2_form: bad arguments");
   const bool two_bytes = dtype == MOEINF_DTYPE_BF16 || dtype == MOEINF_DTYPE_F16;
@@ -437,8 +458,8 @@ static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine*
   TRYHIP(hipMemset(g->d_n_active, 0, sizeof(int32_t)));
   TRY(alloc_token_workspace(g, cfg->max_tokens));
   if (g->has_shared) {
-    TRYHIP(hipMalloc(&g->d_h_sh, (size_t)kHideSharedMaxTokens * g->Fs * g->es));
-    TRYHIP(hipMalloc(&g->d_y_sh, (size_t)kHideSharedMaxTokens * g->H * g->es));
+    TRYHIP(hipMalloc(&g->d_h_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->Fs * g->es));
+    TRYHIP(hipMalloc(&g->d_y_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->H * g->es));
   }
   for (int i = 0; i < 4; ++i) g->stage_bytes = std::max<int64_t>(g->stage_bytes, std::max(align_up(g->lay.size[i], kAioAlignment), align_up(g->lay_sh.size[i] * (g->host_f8 ? 2 : 1), kAioAlignment)));
   {
@@ -1085,13 +1106,6 @@ int pump_if_pending(moeinf_engine* g) {
   if (g->pq.empty() && g->prefetch_inflight.empty() && g->disk_inflight.empty() && g->stale_disk.empty()) return MOEINF_OK;
   return pump_prefetch(g);
 }
-// FfnStage::fuse_combine: 1 = the hand-off rows leave as sixteen 2-byte write-through stores; 2 (MOEINF_WIDE_OUT=1) = gathered
-// through LDS into 16-byte ones — measured SLOWER (DeepSeek-V2-Lite 1.031/1.038 vs 1.022/1.031 ms/token, stage 2 +0.6 us: the
-// extra LDS round trip and barrier cost more than the fabric writes they save), so off by default
-static int fuse_mode() {
-  static const int m = (getenv("MOEINF_WIDE_OUT") && atoi(getenv("MOEINF_WIDE_OUT")) != 0) ? 2 : 1;
-  return m;
-}
 void fill_stage(const moeinf_engine* g, int layer, int stage, FfnStage& s, int64_t ld_x) {
   const DevLayout& b = g->dlay;
   const DevLayout& bs = g->dlay_sh;
@@ -1134,10 +1148,10 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   const moeinf_profile p0 = g->prof;
   int64_t U = 0, rows = 0;
   for (int e = 0; e < E; ++e) { if (mirror[1 + e] > 0) { ++U; rows += mirror[1 + e]; } }
-  const bool hidden = g->has_shared && local && g->last_hidden_shared;  // the shared expert ran inside the router launches
+  const bool hidden = g->has_shared && local && g->last_form.hide_shared;  // the shared expert ran inside the router launches
   const int64_t es = g->es, H = g->H, F = g->F, Fs = g->Fs, Tsh = (g->has_shared && local && !hidden) ? T : 0;
   // a self-routing forward carries the hidden shared expert's stage 2 inside the FFN stage-1 launch
-  const bool sr2 = hidden && g->last_selfroute;
+  const bool sr2 = hidden && g->last_form.selfroute;
   if (hidden) g->prof.route_bytes += (sr2 ? 2 : 3) * Fs * H * es + (int64_t)T * ((sr2 ? 1 : 2) * Fs + (sr2 ? 1 : 2) * H) * es;
   if (sr2) g->prof.ffn1_bytes += Fs * H * es + (int64_t)T * (Fs + H) * es;
   const int et = g->cfg.expert_type;
@@ -1155,12 +1169,12 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   }
   g->prof.forwards += 1;
   if (mirror[0] > 0) { g->prof.ffn1_launches += 1; g->prof.ffn2_launches += 1; }
-  if (local && g->last_front1 && !g->last_layer1) {
+  if (local && g->last_form.stage1 == ST_FRONT1) {
     // the gate (and the hidden shared expert's first stage) ran inside the launch timed as "ffn1": their bytes belong there
     g->prof.ffn1_bytes += g->prof.route_bytes - p0.route_bytes;
     g->prof.route_bytes = p0.route_bytes;
   }
-  if (local && g->last_layer1) {
+  if (local && g->last_form.stage1 == ST_LAYER1_SWITCH) {
     // the one-launch layer: every byte of the forward moves inside the launch timed as "ffn1" (the other intervals are empty)
     g->prof.ffn1_bytes = p0.ffn1_bytes + (g->prof.ffn1_bytes - p0.ffn1_bytes) + (g->prof.ffn2_bytes - p0.ffn2_bytes) + (g->prof.route_bytes - p0.route_bytes) +
                          (g->prof.combine_bytes - p0.combine_bytes);
@@ -1419,7 +1433,7 @@ static int lookahead_issue(moeinf_engine* g, int layer) {
 // chunk may recycle its slots once its kernels have drained.
 static int run_experts(moeinf_engine* g, int layer, const void* x_in, hipStream_t st, hipEvent_t ev_before,
                        hipEvent_t ev_mid, hipEvent_t ev_after, int64_t ld_x = 0, const CombineArgs* fuse = nullptr,
-                       bool* fused = nullptr, int rows_hint = 0) {
+                       int fuse_mode = 0, bool* fused = nullptr, int rows_hint = 0) {
   const int E = g->E, E1 = E + 1;
   const int na = g->h_mirror[0];
   const int32_t* active = g->h_mirror + 1 + E1;
@@ -1446,7 +1460,7 @@ static int run_experts(moeinf_engine* g, int layer, const void* x_in, hipStream_
     s1.active = g->d_active + a; s2.active = g->d_active + a;
     s1.n_active_host = b - a; s2.n_active_host = b - a;
     if (fuse && a == 0 && b == na && na > 0) {  // one chunk: the last column-tile block of stage 2 combines
-      s2.fuse_combine = fuse_mode(); s2.tile_done = g->d_arrive; s2.comb = *fuse;
+      s2.fuse_combine = fuse_mode; s2.tile_done = g->d_arrive; s2.comb = *fuse;
       if (fused) *fused = true;
     }
     // the exact maximum, but never below the estimate the sync-free path passes for the same forward (rows_hint): both paths
@@ -1475,7 +1489,7 @@ static int run_experts(moeinf_engine* g, int layer, const void* x_in, hipStream_
 //   Decision path: some expert may be missing: small pinned D2H + event wait, then fetch/evict.
 int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x, int T, int max_active, int exp_rows,
                             hipStream_t st, bool prof, moeinf_engine::ProfRec* pr, const MirrorPlan& mp,
-                            const CombineArgs* fuse, bool* fused, const SelfRoute* sr) {
+                            const CombineArgs* fuse, bool* fused, const LayerForm& lf, const SelfRoute* sr) {
   const int E = g->E, E1 = E + 1;
   if (fused) *fused = false;
   if (mp.fast) {
@@ -1494,76 +1508,49 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
     fill_stage(g, layer, 1, s1, ld_x);
     s1.in = x_in;
     fill_stage(g, layer, 2, s2);
-    if (fuse) { s2.fuse_combine = fuse_mode(); s2.tile_done = g->d_arrive; s2.comb = *fuse; if (fused) *fused = true; }
-    // decode launchers that carry the timer on their own dispatch packet: no event-record packets inside the interval
-    // (every FFN-stage launcher is ONE launch and carries the timer; the small-batch self-routing stage 1 is the exception)
-    const bool kt1 = prof && !(sr && !sr->layer1_switch && !sr->front1 && T > 1);
-    const bool kt2 = prof;
+    if (fuse) { s2.fuse_combine = lf.fuse_mode; s2.tile_done = g->d_arrive; s2.comb = *fuse; if (fused) *fused = true; }
+    const bool kt1 = prof && lf.kt1, kt2 = prof;  // (layer_form: which stage-1 launchers carry the timer on their own dispatch packet)
     if (prof && !kt1) HIPCHK(hipEventRecord(pr->ev[2], st));
-    if (sr && sr->layer1_switch) {
-      LayerSync sy;
-      memset(&sy, 0, sizeof sy);
+    LayerSync sy;
+    memset(&sy, 0, sizeof sy);
+    if (lf.stage1 == ST_LAYER1_SWITCH || lf.stage1 == ST_FRONT1) {
       sy.ctr = g->d_layer_ctr; sy.launch = g->layer1_launches + 1; sy.timeout_ticks = g->layer1_timeout_ticks; sy.err = g->d_miss; sy.err_host = g->h_miss;
-      static const int l1_sleep = getenv("MOEINF_LAYER1_SLEEP") ? std::max(1, atoi(getenv("MOEINF_LAYER1_SLEEP"))) : 2;
-      sy.sleep = l1_sleep; sy.scalar_poll = g->layer1_scalar_poll ? 1 : 0;
-      if (g->layer1_switch_wgs_per_cu < 0) g->layer1_switch_wgs_per_cu = layer1_switch_wgs_per_cu(sr->ra->x_dtype, sr->ra->gate_dtype);  // asked once: registers + LDS of the instantiation
-      const int ncu = g->num_cus;
+      sy.sleep = lf.poll_sleep; sy.scalar_poll = g->layer1_scalar_poll ? 1 : 0;
       if (getenv("MOEINF_LAYER1_TRACE")) {
-        const int nb = g->E + 1 + (g->F + 15) / 16 + 4 * ((g->H + 15) / 16);
+        const int nb = lf.stage1 == ST_LAYER1_SWITCH ? g->E + 1 + (g->F + 15) / 16 + 4 * ((g->H + 15) / 16)
+                                                     : g->E + (sr->sh1 ? (g->Fs + 15) / 16 : 0) + 1 + g->K * ((g->F + 15) / 16) + (sr->sh2 ? (g->H + 15) / 16 : 0);
         if (!g->d_layer_trace) { if (hipMalloc((void**)&g->d_layer_trace, (size_t)nb * 32) != hipSuccess) g->d_layer_trace = nullptr; else (void)hipMemset(g->d_layer_trace, 0, (size_t)nb * 32); g->layer1_trace_blocks = nb; }
         sy.trace = g->d_layer_trace;
       }
-      if (!g->d_layer_part) { if (hipMalloc((void**)&g->d_layer_part, (size_t)4 * g->H * sizeof(float)) != hipSuccess) { g->d_layer_part = nullptr; (void)hipGetLastError(); } }
-      sy.part = g->d_layer_part;
-      if (kt1 && fuse) arm_kernel_timer(pr->ev[2], pr->ev[3]);
-      const bool one_launch = fuse && launch_moe_layer1_switch(*sr->ra, *sr->ia, s1, s2, sy, ncu, g->layer1_switch_wgs_per_cu, st);
-      disarm_kernel_timer();  // (declined or failed before taking it: the self-routing stage 1 below arms its own)
-      if (one_launch) {
-        g->layer1_launches += 1;
-        if (prof) { HIPCHK(hipEventRecord(pr->ev[4], st)); g->prof.kernel_timed_launches += 1; }
-        return MOEINF_OK;
-      }
-      (void)hipGetLastError();
-      g->last_layer1 = false;  // declined (fewer CUs than workgroups, ...): the three launches, starting with the gate the caller left out
-      HIPCHK(launch_gate_logits(*sr->ra, st));
     }
-    if (sr && sr->front1) {
-      LayerSync sy;
-      memset(&sy, 0, sizeof sy);
-      sy.ctr = g->d_layer_ctr; sy.launch = g->layer1_launches + 1; sy.timeout_ticks = g->layer1_timeout_ticks; sy.err = g->d_miss; sy.err_host = g->h_miss;
-      static const int f1_sleep = getenv("MOEINF_LAYER1_SLEEP") ? std::max(1, atoi(getenv("MOEINF_LAYER1_SLEEP"))) : 2;
-      sy.sleep = f1_sleep; sy.scalar_poll = g->layer1_scalar_poll ? 1 : 0;
-      if (getenv("MOEINF_LAYER1_TRACE")) {
-        const int nb = g->E + (sr->sh1 ? (g->Fs + 15) / 16 : 0) + 1 + g->K * ((g->F + 15) / 16) + (sr->sh2 ? (g->H + 15) / 16 : 0);
-        if (!g->d_layer_trace) { if (hipMalloc((void**)&g->d_layer_trace, (size_t)nb * 32) != hipSuccess) g->d_layer_trace = nullptr; else (void)hipMemset(g->d_layer_trace, 0, (size_t)nb * 32); g->layer1_trace_blocks = nb; }
-        sy.trace = g->d_layer_trace;
-      }
+    if (lf.stage1 == ST_LAYER1_SWITCH && !g->d_layer_part) HIPCHK(hipMalloc((void**)&g->d_layer_part, (size_t)4 * g->H * sizeof(float)));
+    if (kt1) arm_kernel_timer(pr->ev[2], pr->ev[3]);  // (nothing between here and disarm_kernel_timer returns)
+    hipError_t le = hipErrorInvalidValue;
+    switch (lf.stage1) {
+      // the whole layer.  layer_form has checked that the launcher takes the shape: a launch it declines or that fails is an error
+      case ST_LAYER1_SWITCH:
+        sy.part = g->d_layer_part;
+        le = launch_moe_layer1_switch(*sr->ra, *sr->ia, s1, s2, sy, g->num_cus, g->layer1_switch_wgs_per_cu, st) ? hipSuccess : hipErrorInvalidValue;
+        break;
       // (a physical workgroup order that evens out the bytes per CU was measured in round 6: slower, profiles/r06_deepseek_front1_balanced_order_rejected.txt)
-      if (kt1) arm_kernel_timer(pr->ev[2], pr->ev[3]);
-      const hipError_t le = launch_moe_front1(*sr->ra, *sr->ia, sr->sh1, sr->sh2, s1, sy, st);
-      disarm_kernel_timer();
-      HIPCHK(le);
-      g->layer1_launches += 1;  // only a launch that went out moves the grow-only counters' target (a failed one must not leave them out of step)
-    } else if (sr && T > 1) HIPCHK(launch_ffn1_selfroute_multi(*sr->ra, *sr->ia, s1, sr->sh2, std::min(E, T * g->K), st));
-    else if (sr) {
-      if (kt1) arm_kernel_timer(pr->ev[2], pr->ev[3]);
-      const hipError_t le = launch_ffn1_selfroute(*sr->ra, *sr->ia, s1, sr->sh2, st);
-      disarm_kernel_timer();
-      HIPCHK(le);
+      case ST_FRONT1: le = launch_moe_front1(*sr->ra, *sr->ia, sr->sh1, sr->sh2, s1, sy, lf.sr, st); break;
+      case ST_SELFROUTE_MULTI: le = launch_ffn1_selfroute_multi(*sr->ra, *sr->ia, s1, sr->sh2, std::min(E, T * g->K), lf.sr, st); break;
+      case ST_SELFROUTE: le = launch_ffn1_selfroute(*sr->ra, *sr->ia, s1, sr->sh2, lf.sr, st); break;
+      case ST_GENERIC: le = launch_ffn_stage(s1, max_active, exp_rows, g->num_cus, st); break;
     }
-    else {
-      if (kt1) arm_kernel_timer(pr->ev[2], pr->ev[3]);
-      const hipError_t le = launch_ffn_stage(s1, max_active, exp_rows, g->num_cus, st);
-      disarm_kernel_timer();
-      HIPCHK(le);
+    disarm_kernel_timer();  // (after a launch that failed before taking it)
+    HIPCHK(le);
+    // only a launch that went out moves the grow-only counters' target (a failed one must not leave them out of step)
+    if (lf.stage1 == ST_LAYER1_SWITCH || lf.stage1 == ST_FRONT1) g->layer1_launches += 1;
+    if (lf.stage2 == ST_NONE) {  // the one-launch layer
+      if (prof) { HIPCHK(hipEventRecord(pr->ev[4], st)); g->prof.kernel_timed_launches += 1; }
+      return MOEINF_OK;
     }
     if (prof && !kt1) HIPCHK(hipEventRecord(pr->ev[3], st));
-    {
-      if (kt2 && (pr->k2 = get_event(g))) arm_kernel_timer(pr->k2, pr->ev[4]);
-      const hipError_t le = (sr && fuse && T == 1) ? launch_ffn2_decode1(s2, st) : launch_ffn_stage(s2, max_active, exp_rows, g->num_cus, st);
-      disarm_kernel_timer();
-      HIPCHK(le);
-    }
+    if (kt2 && (pr->k2 = get_event(g))) arm_kernel_timer(pr->k2, pr->ev[4]);
+    le = lf.stage2 == ST_DECODE1 ? launch_ffn2_decode1(s2, lf.dec1, st) : launch_ffn_stage(s2, max_active, exp_rows, g->num_cus, st);
+    disarm_kernel_timer();
+    HIPCHK(le);
     if (prof && !(kt2 && pr->k2)) HIPCHK(hipEventRecord(pr->ev[4], st));
     if (prof) g->prof.kernel_timed_launches += (kt1 ? 1 : 0) + ((kt2 && pr->k2) ? 1 : 0);
   } else {
@@ -1601,7 +1588,7 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
       }
       g->la_armed_T = 0;
     }
-    CHK(run_experts(g, layer, x_in, st, prof ? pr->ev[2] : nullptr, prof ? pr->ev[3] : nullptr, prof ? pr->ev[4] : nullptr, ld_x, fuse, fused, exp_rows));
+    CHK(run_experts(g, layer, x_in, st, prof ? pr->ev[2] : nullptr, prof ? pr->ev[3] : nullptr, prof ? pr->ev[4] : nullptr, ld_x, fuse, lf.fuse_mode, fused, exp_rows));
   }
   return MOEINF_OK;
 }
@@ -1627,13 +1614,24 @@ void make_index_args(const moeinf_engine* g, int T, int batch_rows, int32_t* mir
   ia.counts = g->d_counts; ia.offsets = g->d_offsets; ia.active = g->d_active; ia.n_active = g->d_n_active;
   ia.pair_slot = g->d_pair_slot; ia.slot_token = g->d_slot_token; ia.slot_pair = g->d_slot_pair; ia.mirror = mirror;
 }
-// decode-sized DeepSeek forwards: the shared expert (routing-independent, always resident) runs INSIDE the two router launches
-bool can_hide_shared(const moeinf_engine* g, int T) {
-  static const bool hide_env = getenv("MOEINF_HIDE_SHARED") ? atoi(getenv("MOEINF_HIDE_SHARED")) != 0 : true;
-  // (fp16 since round 5: gate_shared1 / route_shared2 / moe_front1 on half_t; fp32 experts keep the shared expert behind the router)
-  // (the gate is in the model dtype or fp32: moeinf_create refuses the mixed pairs)
-  return hide_env && g->has_shared && (g->dt == DT_BF16 || g->dt == DT_F16) && T <= kHideSharedMaxTokens && T * g->K <= 64 && g->cfg.router_kind == MOEINF_ROUTER_DEEPSEEK;
+static_assert(RK_MIXTRAL == MOEINF_ROUTER_MIXTRAL && RK_DEEPSEEK == MOEINF_ROUTER_DEEPSEEK && RK_SWITCH == MOEINF_ROUTER_SWITCH &&
+              ET_SWITCH == MOEINF_EXPERT_SWITCH && ET_MIXTRAL == MOEINF_EXPERT_MIXTRAL && ET_DEEPSEEK == MOEINF_EXPERT_DEEPSEEK &&
+              LAYER_ROUTE_ONLY == MOEINF_FWD_ROUTE_ONLY && LAYER_NO_COMBINE == MOEINF_FWD_NO_COMBINE,
+              "kernels.h mirrors include/moeinf.h");
+// what layer_form (kernels.h) reads of a forward of T tokens
+static LayerShape layer_shape(const moeinf_engine* g, int T, uint32_t flags, bool masked, bool fast) {
+  LayerShape s;
+  s.router_kind = g->cfg.router_kind; s.expert_type = g->cfg.expert_type;
+  s.dtype = g->dt; s.slot_dtype = g->slot_dt;
+  s.gate_dtype = g->cfg.gate_dtype == MOEINF_DTYPE_BF16 ? DT_BF16 : (g->cfg.gate_dtype == MOEINF_DTYPE_F16 ? DT_F16 : DT_F32);
+  s.T = T; s.K = g->K; s.E = g->E; s.H = g->H; s.F = g->F; s.Fs = g->Fs;
+  s.has_shared = g->has_shared ? 1 : 0; s.n_group = g->cfg.n_group; s.v3 = g->route_v3 ? 1 : 0;
+  s.capacity = g->cfg.router_kind == MOEINF_ROUTER_SWITCH ? g->cfg.expert_capacity : 0;
+  s.flags = (int)(flags & (MOEINF_FWD_ROUTE_ONLY | MOEINF_FWD_NO_COMBINE)); s.masked = masked ? 1 : 0; s.fast = fast ? 1 : 0;
+  s.ovr_out = g->ovr_out ? 1 : 0; s.num_cus = g->num_cus; s.l1_wgs_per_cu = std::max(0, g->layer1_switch_wgs_per_cu);
+  return s;
 }
+bool can_hide_shared(const moeinf_engine* g, int T) { return can_hide_shared(layer_shape(g, T, 0, false, false), layer_knobs()); }
 void hidden_shared_stages(const moeinf_engine* g, int layer, const void* x_dev, FfnStage& sh1, FfnStage& sh2) {
   fill_stage(g, layer, 1, sh1, 0);
   sh1.in = x_dev; sh1.row_map = nullptr; sh1.out = g->d_h_sh; sh1.ld_out = g->Fs;
@@ -1716,73 +1714,26 @@ static int moe_forward(moeinf_engine* g, int layer, const void* x_dev, int token
 
   IndexArgs ia;
   make_index_args(g, T, batch_rows, mp.target, ia);
-  // decode-sized DeepSeek forwards: the shared expert (routing-independent, always resident) runs INSIDE the two router
-  // launches instead of behind them
-  const bool hide_shared = !route_only && can_hide_shared(g, T);
-  g->last_hidden_shared = hide_shared;
-  // batch-1 decode on the sync-free path (gated families, bf16): no top-k/index launch at all — FFN stage 1 routes for
-  // itself from the gate logits (ffn1_selfroute_kernel) and one extra block of it writes the routing outputs
-  static const bool selfroute_env = getenv("MOEINF_SELFROUTE") ? atoi(getenv("MOEINF_SELFROUTE")) != 0 : true;
-  const int et_ = g->cfg.expert_type;
-  const bool sr_gated = g->dt != DT_F32 &&
-                        (g->cfg.router_kind == MOEINF_ROUTER_MIXTRAL || (g->cfg.router_kind == MOEINF_ROUTER_DEEPSEEK && g->cfg.n_group <= 1 && !g->route_v3)) &&
-                        (et_ == MOEINF_EXPERT_MIXTRAL || et_ == MOEINF_EXPERT_DEEPSEEK) && (!g->has_shared || hide_shared);
-  // (round 4) Switch: top-1, plain ReLU experts, bf16 or fp32; a single token can never exceed the per-row capacity
-  const bool sr_switch = g->cfg.router_kind == MOEINF_ROUTER_SWITCH && et_ == MOEINF_EXPERT_SWITCH && K == 1 && !g->has_shared &&
-                         (flags & MOEINF_FWD_NO_COMBINE) == 0 && ia.capacity != 0 && fuse_mode() != 0;
-  // (round 4) decode batches of 2..8 tokens of the gated families: the same idea, every workgroup routes every token
-  // Measured (profiles/r04_small_batch_selfroute.txt): DeepSeek-V2-Lite batch 2 / 4: 1.530 -> 1.373 / 2.163 -> 2.056 ms per step;
-  // batch 8 (48 pairs over 64 experts): 3.17 -> 3.61 — every workgroup of the worst-case grid (48 expert slots) pays eight
-  // routings before it knows that its slot is empty.  Hence at most 24 (token, expert) pairs; Mixtral (8 experts, all of them
-  // active from batch 4 on) gains 2.3 / 0.9 / 0.6 % at batch 2 / 4 / 8.
-  static const int sr_multi_env = getenv("MOEINF_SELFROUTE_MULTI") ? atoi(getenv("MOEINF_SELFROUTE_MULTI")) : 8;
-  static const int sr_multi_pairs = getenv("MOEINF_SELFROUTE_MULTI_PAIRS") ? atoi(getenv("MOEINF_SELFROUTE_MULTI_PAIRS")) : 24;
-  const bool sr_multi = T >= 2 && T <= std::min(8, sr_multi_env) && T * K <= std::min(64, sr_multi_pairs) && sr_gated;
-  // A token mask takes the generic router launches (route_core reads the mask): the self-routing forms (selfroute, multi,
-  // moe_front1, the Switch one-launch layer) and the fused combine assume every token keeps its K experts, so stage 2 always runs.
-  const bool selfroute = selfroute_env && !token_mask && !route_only && mp.fast && K <= 8 && E <= 64 && !g->ovr_out &&
-                         ((T == 1 && (sr_gated || sr_switch)) || sr_multi);
-  g->last_selfroute = selfroute;
-  // (the whole DeepSeek layer as ONE persistent launch was built in round 5, measured slower — 1.09 vs 0.958 ms/token — and
-  // removed in round 6: DESIGN.md section 4.5.1 keeps the analysis)
-  // Switch (top-1, no shared expert): the one-launch form is the DEFAULT — three launches of 3-10 us for 18.9 MB are pure fixed
-  // cost, and with hardly any traffic in flight a flag costs ~1 us (MOEINF_LAYER1_SWITCH=0: the three launches)
-  static const bool layer1s_env = getenv("MOEINF_LAYER1_SWITCH") ? atoi(getenv("MOEINF_LAYER1_SWITCH")) != 0 : true;
-  const bool layer1_switch = layer1s_env && selfroute && T == 1 && sr_switch && !sr_gated && !(flags & MOEINF_FWD_NO_COMBINE) && g->dt != DT_F16;
-  g->last_layer1 = layer1_switch;
-  // the gated families: the gate (and the hidden shared expert) can ride in FRONT of the self-routing stage 1, in the same
-  // launch (round 5, launch_moe_front1).  Measured A/B/A/B (profiles/r05_front1_gate_and_stage1_in_one_launch.txt): DeepSeek-V2-Lite
-  // 0.949-0.967 -> 0.937 ms/token (two launches per layer instead of three) = the default with a hidden shared expert; Mixtral
-  // 3.708-3.726 -> 3.723-3.728 (nothing: the hop costs what the gate launch cost) = off unless MOEINF_FRONT1=1; =0: never
-  static const int front1_env = getenv("MOEINF_FRONT1") ? atoi(getenv("MOEINF_FRONT1")) : -1;
-  g->last_front1 = false;
-  const bool front1 = (front1_env < 0 ? hide_shared : front1_env != 0) && selfroute && T == 1 && sr_gated && g->dt != DT_F32 &&
-                      (hide_shared || !g->has_shared) && (ra.gate_dtype == ra.x_dtype || ra.gate_dtype == DT_F32);
+  // Switch batch 1: the one-launch layer must fit the chip at once — its occupancy is asked once (registers + LDS of the instantiation)
+  if (g->layer1_switch_wgs_per_cu < 0 && T == 1 && g->cfg.router_kind == MOEINF_ROUTER_SWITCH && !route_only)
+    g->layer1_switch_wgs_per_cu = layer1_switch_wgs_per_cu(ra.x_dtype, ra.gate_dtype);
+  // which launches make up this forward, and the form of each: ONE pure function (kernels.h)
+  const LayerForm lf = layer_form(layer_shape(g, T, flags, token_mask != nullptr, mp.fast), layer_knobs());
+  g->last_form = lf;
+  const bool hide_shared = lf.hide_shared;
   FfnStage sh1, sh2;
   if (hide_shared) {
     hidden_shared_stages(g, layer, x_dev, sh1, sh2);
     ia.shared = 0;  // the index lists routed experts only
   }
-  g->last_front1 = front1;
-  if (layer1_switch || front1) {
-    // nothing here: dispatch_experts launches the layer / the launch that carries the gate
-  } else if (selfroute) {
-    if (hide_shared) HIPCHK(launch_gate_shared1(ra, sh1, st));
-    else HIPCHK(launch_gate_logits(ra, st));
-  } else if (hide_shared) {
-    HIPCHK(launch_gate_shared1(ra, sh1, st));
-    HIPCHK(launch_route_shared2(ra, ia, sh2, st));
-  } else {
-    HIPCHK(launch_gate_logits(ra, st));
-    if (T <= 64) {
-      HIPCHK(launch_route_index(ra, ia, st));  // decode: top-k + dispatch index in one launch
-    } else {
-      HIPCHK(launch_route_topk(ra, st));
-      // long prefills: the index over many workgroups (one workgroup walks 1024-pair chunks serially, ~12 us each)
-      static const int wide_pairs = getenv("MOEINF_INDEX_WIDE_PAIRS") ? atoi(getenv("MOEINF_INDEX_WIDE_PAIRS")) : 2048;
-      if (ia.capacity <= 0 && (int64_t)T * K > wide_pairs) HIPCHK(launch_dispatch_index_wide(ia, g->d_chunk, st));
-      else HIPCHK(launch_dispatch_index(ia, st));
-    }
+  switch (lf.router) {
+    case ROUTER_NONE: break;  // dispatch_experts launches the layer / the launch that carries the gate
+    case ROUTER_GATE: HIPCHK(launch_gate_logits(ra, st)); break;
+    case ROUTER_GATE_SHARED1: HIPCHK(launch_gate_shared1(ra, sh1, st)); break;
+    case ROUTER_GATE_SHARED1_ROUTE_SHARED2: HIPCHK(launch_gate_shared1(ra, sh1, st)); HIPCHK(launch_route_shared2(ra, ia, sh2, st)); break;
+    case ROUTER_GATE_ROUTE_INDEX: HIPCHK(launch_gate_logits(ra, st)); HIPCHK(launch_route_index(ra, ia, st)); break;
+    case ROUTER_GATE_TOPK_INDEX: HIPCHK(launch_gate_logits(ra, st)); HIPCHK(launch_route_topk(ra, st)); HIPCHK(launch_dispatch_index(ia, st)); break;
+    case ROUTER_GATE_TOPK_WIDE: HIPCHK(launch_gate_logits(ra, st)); HIPCHK(launch_route_topk(ra, st)); HIPCHK(launch_dispatch_index_wide(ia, g->d_chunk, st)); break;
   }
   // next-layer gate lookahead: the decision path waits for this layer's routing anyway — layer l+1's gate over the same
   // rows rides in front of that wait (two small launches; the top-k lands in pinned memory)
@@ -1815,17 +1766,11 @@ static int moe_forward(moeinf_engine* g, int layer, const void* x_dev, int token
   ca.shared_offsets = (g->has_shared && !hide_shared) ? g->d_offsets : nullptr;  // shared rows start at offsets[E] (hidden: row 0 of y_shared)
   ca.shared_E = E;
   ca.T = T; ca.H = g->H; ca.K = K; ca.kind = g->cfg.router_kind; ca.dtype = g->dt;
-  // decode-sized Mixtral/DeepSeek forwards (every token keeps K experts, so stage 2 always runs): the combine
-  // rides in the epilogue of FFN stage 2
-  static const bool fuse_combine = getenv("MOEINF_FUSE_COMBINE") ? atoi(getenv("MOEINF_FUSE_COMBINE")) != 0 : true;
-  const bool can_fuse = fuse_combine && want_combine && T <= 16 && !token_mask &&
-                        (g->cfg.router_kind == MOEINF_ROUTER_MIXTRAL || g->cfg.router_kind == MOEINF_ROUTER_DEEPSEEK ||
-                         (selfroute && sr_switch));  // (Switch: only the batch-1 stage 2 knows its combine)
   bool fused = false;
-  SelfRoute sr{&ra, &ia, hide_shared ? &sh2 : nullptr, hide_shared ? &sh1 : nullptr, front1, layer1_switch};
+  const SelfRoute sr{&ra, &ia, hide_shared ? &sh2 : nullptr, hide_shared ? &sh1 : nullptr};
   CHK(dispatch_experts(g, layer, x_dev, 0, T, std::min(E, T * K) + ((g->has_shared && !hide_shared) ? 1 : 0),
                        rows_estimate(T, K, E), st, prof, prof ? &pr : nullptr,
-                       mp, can_fuse ? &ca : nullptr, &fused, selfroute ? &sr : nullptr));
+                       mp, lf.can_fuse_combine ? &ca : nullptr, &fused, lf, lf.selfroute ? &sr : nullptr));
   strace.mark("dispatch_experts");
   if (want_combine && !fused) HIPCHK(launch_combine(ca, st));
   if (prof) { HIPCHK(hipEventRecord(pr.ev[5], st)); g->prof_pending.push_back(pr); }
@@ -2018,7 +1963,7 @@ extern "C" int moeinf_get_expert_outputs(moeinf_engine* g, void* host_out, int64
   const int64_t rows = (int64_t)g->last_T * g->K + (g->has_shared ? g->last_T : 0);
   const int64_t need = rows * g->H * g->es;
   if (!host_out || nbytes > need || nbytes <= 0) return fail(MOEINF_ERR_INVALID, "nbytes must be in 1..%lld", (long long)need);
-  if (g->has_shared && g->last_hidden_shared) {
+  if (g->has_shared && g->last_form.hide_shared) {
     // routed rows sit in y, the shared expert's rows (computed inside the router launches) in their own buffer
     int32_t routed = 0;
     HIPCHK(hipMemcpy(&routed, g->d_offsets + g->E, sizeof routed, hipMemcpyDeviceToHost));
@@ -2357,7 +2302,7 @@ extern "C" int moeinf_reserve_tokens(moeinf_engine* g, int max_tokens) {
 
 
 int launch_index_auto(moeinf_engine* g, const IndexArgs& ia, hipStream_t st) {
-  if (ia.capacity <= 0 && (int64_t)ia.T * ia.K > 2048) HIPCHK(launch_dispatch_index_wide(ia, g->d_chunk, st));
+  if (index_is_wide(ia.capacity, (int64_t)ia.T * ia.K, layer_knobs())) HIPCHK(launch_dispatch_index_wide(ia, g->d_chunk, st));
   else HIPCHK(launch_dispatch_index(ia, st));
   return MOEINF_OK;
 }

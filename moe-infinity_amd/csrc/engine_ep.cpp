@@ -102,8 +102,8 @@ static int ep_route_pack_impl(moeinf_engine* g, int layer, const void* x_dev, in
   make_index_args(g, T, batch_rows, nullptr, ia);
   ia.shared = 0;  // the owner-side index is built from the received rows; the shared expert never crosses the fabric
   const bool hide_shared = can_hide_shared(g, T);
-  g->last_hidden_shared = hide_shared;
-  g->last_selfroute = false;
+  g->last_form = LayerForm();
+  g->last_form.hide_shared = hide_shared;
   // the pack rides in the router's single-workgroup launch while the rows are few KB (one workgroup copies them)
   static const int fuse_kb = getenv("MOEINF_EP_FUSE_PACK_KB") ? atoi(getenv("MOEINF_EP_FUSE_PACK_KB")) : 64;
   const bool fuse = np <= 64 && T <= 64 && (int64_t)np * g->H * g->es <= (int64_t)fuse_kb * 1024;
@@ -273,7 +273,7 @@ static int ep_combine_impl(moeinf_engine* g, const void* x_dev, const void* ret_
   if (!g->d_ep_pair_pos || cap_rows != g->ep_cap_rows) return fail(MOEINF_ERR_STATE, "ep_combine needs a preceding ep_pack with the same cap_rows (0 after ep_pack_compact)");
   DeviceScope on_dev_(g->cfg.device_id); HIPCHK(on_dev_.err);
   hipStream_t st = (hipStream_t)stream;
-  if (g->has_shared && !g->last_hidden_shared) {
+  if (g->has_shared && !g->last_form.hide_shared) {
     // the shared expert (always resident, replicated on every rank) runs on this rank's own tokens; for decode-sized
     // forwards it already ran inside the router launches of moeinf_ep_route_pack, i.e. UNDER the exchange
     const int T = g->last_T;
@@ -296,7 +296,7 @@ static int ep_combine_impl(moeinf_engine* g, const void* x_dev, const void* ret_
   memset(&ca, 0, sizeof ca);
   ca.x = x_dev; ca.y = ret_dev; ca.out = out_dev;
   ca.topk_idx = g->d_topk_idx; ca.topk_w = g->d_topk_w; ca.pair_slot = g->d_ep_pair_pos; ca.pair_order = g->d_pair_order;
-  ca.router_prob = g->d_router_prob; ca.y_shared = g->has_shared ? (g->last_hidden_shared ? g->d_y_sh : g->d_y) : nullptr; ca.shared_offsets = nullptr; ca.shared_E = g->E;
+  ca.router_prob = g->d_router_prob; ca.y_shared = g->has_shared ? (g->last_form.hide_shared ? g->d_y_sh : g->d_y) : nullptr; ca.shared_offsets = nullptr; ca.shared_E = g->E;
   ca.T = g->last_T; ca.H = g->H; ca.K = g->K; ca.kind = g->cfg.router_kind; ca.dtype = g->dt;
   if (pv) {  // the owners' outputs of exchange `epoch` must have landed in this rank's return region
     EpWait w{g->ep_win.ret_flags(), pv->size, pv->epoch, pv->timeout_ticks, pv->err};
@@ -581,14 +581,14 @@ static int ep_peer_forward_bcast(moeinf_engine* g, int layer, const void* x_dev,
   EpBcastArgs b;
   memset(&b, 0, sizeof b);
   b.x = x_dev; b.pair_pos = g->d_ep_pair_pos; b.peers = pv;
-  g->last_T = 1; g->last_layer = layer; g->last_stream = st; g->last_selfroute = false;
+  g->last_T = 1; g->last_layer = layer; g->last_stream = st; g->last_form = LayerForm();
   mark(0);
   if (mp.fast) {
     const bool hide = g->has_shared;  // (eligibility says it can be hidden)
     FfnStage sh1, sh2;
     if (hide) { hidden_shared_stages(g, layer, x_dev, sh1, sh2); HIPCHK(launch_gate_shared1(ra, sh1, st)); }
     else HIPCHK(launch_gate_logits(ra, st));
-    g->last_hidden_shared = hide;
+    g->last_form.hide_shared = hide;
     moeinf_engine::PendingMirror pm;
     pm.buf = mp.target; pm.seq = g->seq + 1; pm.layer = layer; pm.T = G; pm.prof = false; pm.local = false;
     g->pend.push_back(pm);
@@ -618,7 +618,7 @@ static int ep_peer_forward_bcast(moeinf_engine* g, int layer, const void* x_dev,
   } else {
     // plan_mirror handed out the engine's own mirror (nothing pooled to give back); the generic owner path plans again
     HIPCHK(launch_gate_logits(ra, st));
-    g->last_hidden_shared = false;  // the shared expert runs on the home rank inside the combine step
+    g->last_form.hide_shared = false;  // the shared expert runs on the home rank inside the combine step
     HIPCHK(launch_ep_bcast(ra, b, st));
     g->st.forwards += 1;
     mark(1); mark(2);

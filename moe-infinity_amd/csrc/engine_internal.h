@@ -186,7 +186,6 @@ struct Slot {
 
 static constexpr int kFenceRing = 64;
 static constexpr int kMirrorPool = 128;  // pooled pinned routing mirrors of sync-free forwards not yet applied to the counters
-static constexpr int kHideSharedMaxTokens = 16;  // forwards up to this many tokens hide the shared expert under the router
 
 // One H2D lane = a copy stream (hipMemcpyAsync, served by an SDMA engine) + a re-tile stream (kernels) + a ring of two
 // staging buffers, each large enough for the biggest tensor of a blob.  Tensor i+1 is copied into the other
@@ -370,11 +369,8 @@ struct moeinf_engine {
   const int32_t* ovr_map = nullptr;
 
   // last forward
-  bool last_hidden_shared = false;
-  bool last_selfroute = false;      // the last forward used the self-routing FFN stage 1 (batch-1 decode)
-  bool last_front1 = false;         // ... or its front (gate, hidden shared expert, stage 1) as one launch (moe_front1_kernel)
-  bool last_layer1 = false;         // ... and ran as ONE launch (layer_fused.hip)
-  uint32_t* d_layer_ctr = nullptr;  // its counters (kernels.h LayerSync): only grow, zeroed at creation and after an error
+  LayerForm last_form;              // what layer_form (kernels.h) chose for it; the expert-parallel route sets hide_shared only
+  uint32_t* d_layer_ctr = nullptr;  // counters of the fused launches (kernels.h LayerSync): only grow, zeroed at creation and after an error
   uint32_t layer1_launches = 0;
   float* d_layer_part = nullptr;    // [4][H] partial sums of the Switch form's split stage 2
   bool layer1_scalar_poll = false;
@@ -468,13 +464,11 @@ struct moeinf_tracer { Tracer* t; };
 
 // ---- hot-path pieces shared between engine.cpp and engine_ep.cpp (defined in engine.cpp) ---------------------------
 struct MirrorPlan { bool fast = false; int32_t* target = nullptr; };
-struct SelfRoute {  // batch-1 decode: FFN stage 1 routes for itself (launch_ffn1_selfroute)
+struct SelfRoute {  // what a self-routing stage 1 (LayerForm::selfroute) needs beside the two FFN stages
   const RouteArgs* ra;
   const IndexArgs* ia;
   const FfnStage* sh2;  // hidden shared expert's stage 2, or nullptr
-  const FfnStage* sh1 = nullptr;  // front1: the hidden shared expert's stage 1
-  bool front1 = false;  // gate + stage 1 (+ the hidden shared expert) as ONE launch (launch_moe_front1): the caller has NOT launched the gate
-  bool layer1_switch = false;  // ... its Switch form (launch_moe_layer1_switch); if that declines, dispatch_experts launches the gate itself
+  const FfnStage* sh1;  // front1: the hidden shared expert's stage 1
 };
 
 template <typename T>
@@ -485,7 +479,7 @@ static inline int dmalloc(T** p, size_t n) {
 bool can_hide_shared(const moeinf_engine* g, int T);
 int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x, int T, int max_active, int exp_rows,
                      hipStream_t st, bool prof, moeinf_engine::ProfRec* pr, const MirrorPlan& mp,
-                     const CombineArgs* fuse, bool* fused, const SelfRoute* sr = nullptr);
+                     const CombineArgs* fuse, bool* fused, const LayerForm& lf = LayerForm(), const SelfRoute* sr = nullptr);
 void drop_stale_prefetches(moeinf_engine* g, int layer);
 void fill_stage(const moeinf_engine* g, int layer, int stage, FfnStage& s, int64_t ld_x = 0);
 int flush_pokes(moeinf_engine* g, hipStream_t st);

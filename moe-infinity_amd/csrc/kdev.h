@@ -340,6 +340,16 @@ __device__ __forceinline__ void f8x16_to_bf16(const u32x4 w, u32x4& lo, u32x4& h
 // consecutive k-tiles with one 4-byte load, and the scales take exactly R * K / 32 bytes (rounded up to one dword per lane).
 struct mx4w_t {};
 template <> struct act_of<mx4w_t> { using type = uint16_t; };
+// the kernels' T of an (activation dtype, slot dtype) pair: f(T{}) with T = f8w_t / mx4w_t for a slot format, else uint16_t (bf16),
+// half_t or float.  f instantiates only what exists for its T (if constexpr) and answers whether it launched.
+template <typename F>
+static inline bool with_kernel_type(int dtype, int wdtype, F&& f) {
+  if (wdtype == moeinf::DT_F8) return f(f8w_t{});
+  if (wdtype == moeinf::DT_MX4) return f(mx4w_t{});
+  if (dtype == moeinf::DT_BF16) return f(uint16_t{});
+  if (dtype == moeinf::DT_F16) return f(half_t{});
+  return f(float{});
+}
 // 32 e2m1 codes (16 bytes, element 2j in the low nibble of byte j) x 2^(b - 127) -> four bf16x8 MFMA fragments (k 0..7, 8..15, 16..23,
 // 24..31 of the lane's thirty-two): v_cvt_scalef32_pk_bf16_fp4 up-casts two elements per instruction with the scale applied by the
 // hardware, exactly (e2m1 x 2^n has two significant bits and fits bf16's exponent range).  b: the e8m0 byte (0 and 255 are outside

@@ -345,6 +345,319 @@ inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus
   return g;
 }
 
+// ---- which launches make up a forward, and which form every decode launcher takes: the other half of the choice, again ONE pure
+// function (layer_form).  moe_forward (engine.cpp) builds a LayerShape, calls it once and executes the answer; the decode launchers
+// map its parts to their instantiations; moeinf_layer_form exports it and tests/test_layer_form_cpu.py pins it against
+// tests/golden/layer_forms.json (recorded from the launches of the control flow it replaced) and DESIGN.md section 4.3.
+
+// every environment knob that steers it (sweeps only): the launch path reads them once per process (layer_knobs), the export per call
+struct LayerKnobs {
+  int hide_shared = 1;             // MOEINF_HIDE_SHARED: 0 = the shared expert always runs behind the router
+  int selfroute = 1;               // MOEINF_SELFROUTE: 0 = never the self-routing stage 1
+  int selfroute_multi = 8;         // MOEINF_SELFROUTE_MULTI: tokens up to which a decode batch self-routes (at most 8; < 2: never)
+  int selfroute_multi_pairs = 24;  // MOEINF_SELFROUTE_MULTI_PAIRS: ... and (token, expert) pairs (at most 64)
+  int layer1_switch = 1;           // MOEINF_LAYER1_SWITCH: 0 = Switch batch 1 as three launches
+  int front1 = -1;                 // MOEINF_FRONT1: 1 / 0 = the gate always / never in stage 1's launch (-1: with a hidden shared expert)
+  int index_wide_pairs = 2048;     // MOEINF_INDEX_WIDE_PAIRS: more pairs than this take the many-workgroup index
+  int fuse_combine = 1;            // MOEINF_FUSE_COMBINE: 0 = the combine is always a launch of its own
+  int wide_out = 0;                // MOEINF_WIDE_OUT: 1 = the fused combine's hand-off rows leave as 16-byte stores (fuse mode 2)
+  int layer1_sleep = 2;            // MOEINF_LAYER1_SLEEP: s_sleep(2) repetitions between two polls of a fused layer's counters (>= 1)
+  int sr_lds_kb = -1;              // MOEINF_SR_LDS_KB: dynamic LDS per self-routing workgroup (-1: by the rule in selfroute_form)
+  int sr_u = 0;                    // MOEINF_SR_U: its tiles per wave, matrix and batch, 8 or 4 (0: by the rule)
+  int sr_order = 0;                // MOEINF_SR_ORDER: 1 = the hidden shared expert's work items are dispatched last
+  int dec1_pair = 1;               // MOEINF_DEC1_PAIR: 0 = always the arrival-counter form; 8 = eight waves per expert (bf16)
+  int dec1_pair_u = 4;             // MOEINF_DEC1_PAIR_U: tiles per wave and batch of the pair form: 2 (bf16) / 4 / 8
+  int dec1_u = 4;                  // MOEINF_DEC1_U: ... of the arrival-counter form, short reductions: 4 / 8 / 12 (bf16)
+  int dec1_switch_u = 12;          // MOEINF_DEC1_SWITCH_U: ... of its Switch form: 12 or 4
+  int sh1_u = 8;                   // MOEINF_SH1_U: tiles per wave, matrix and batch of gate_shared1's four-wave form: 8 or 4
+  int sh1_nw = 8;                  // MOEINF_SH1_NW: its waves per workgroup: 8 or 4
+  int sh2_nw = 8;                  // MOEINF_SH2_NW: waves per workgroup of route_shared2: 4 / 8 / 16
+  int sh2_u = 4;                   // MOEINF_SH2_U: its tiles per wave and batch: 4 or 8
+  int gate_mfma_tiles = 128;       // MOEINF_GATE_MFMA_TILES: 16 x 16 logit tiles from which the gate runs on the fp64 MFMA (0: never)
+  static LayerKnobs from_env() {
+    auto env = [](const char* n, int d) { const char* v = getenv(n); return v ? atoi(v) : d; };
+    LayerKnobs k;
+    k.hide_shared = env("MOEINF_HIDE_SHARED", k.hide_shared); k.selfroute = env("MOEINF_SELFROUTE", k.selfroute);
+    k.selfroute_multi = env("MOEINF_SELFROUTE_MULTI", k.selfroute_multi);
+    k.selfroute_multi_pairs = env("MOEINF_SELFROUTE_MULTI_PAIRS", k.selfroute_multi_pairs);
+    k.layer1_switch = env("MOEINF_LAYER1_SWITCH", k.layer1_switch); k.front1 = env("MOEINF_FRONT1", k.front1);
+    k.index_wide_pairs = env("MOEINF_INDEX_WIDE_PAIRS", k.index_wide_pairs); k.fuse_combine = env("MOEINF_FUSE_COMBINE", k.fuse_combine);
+    k.wide_out = env("MOEINF_WIDE_OUT", k.wide_out);
+    k.layer1_sleep = env("MOEINF_LAYER1_SLEEP", k.layer1_sleep); if (k.layer1_sleep < 1) k.layer1_sleep = 1;
+    k.sr_lds_kb = env("MOEINF_SR_LDS_KB", k.sr_lds_kb); k.sr_u = env("MOEINF_SR_U", k.sr_u); k.sr_order = env("MOEINF_SR_ORDER", k.sr_order);
+    k.dec1_pair = env("MOEINF_DEC1_PAIR", k.dec1_pair); k.dec1_pair_u = env("MOEINF_DEC1_PAIR_U", k.dec1_pair_u);
+    k.dec1_u = env("MOEINF_DEC1_U", k.dec1_u); k.dec1_switch_u = env("MOEINF_DEC1_SWITCH_U", k.dec1_switch_u);
+    k.sh1_u = env("MOEINF_SH1_U", k.sh1_u); k.sh1_nw = env("MOEINF_SH1_NW", k.sh1_nw);
+    k.sh2_nw = env("MOEINF_SH2_NW", k.sh2_nw); k.sh2_u = env("MOEINF_SH2_U", k.sh2_u);
+    k.gate_mfma_tiles = env("MOEINF_GATE_MFMA_TILES", k.gate_mfma_tiles);
+    return k;
+  }
+};
+inline const LayerKnobs& layer_knobs() { static const LayerKnobs k = LayerKnobs::from_env(); return k; }  // the launch path's: read once
+
+// router kinds and expert types as the choice reads them (= MOEINF_ROUTER_* / MOEINF_EXPERT_* of include/moeinf.h; engine.cpp asserts it)
+enum { RK_MIXTRAL = 0, RK_DEEPSEEK = 1, RK_SWITCH = 2 };
+enum { ET_SWITCH = 0, ET_MIXTRAL = 4, ET_DEEPSEEK = 5 };
+constexpr int HIDE_SHARED_MAX_TOKENS = 16;  // forwards up to this many tokens hide the shared expert under the router
+enum { LAYER_ROUTE_ONLY = 1, LAYER_NO_COMBINE = 2 };  // = MOEINF_FWD_*
+
+// the plain values the choice reads: no pointers, no engine
+struct LayerShape {
+  int router_kind = RK_MIXTRAL;  // MOEINF_ROUTER_* as the engine keeps it (V3 and the no-renorm kinds folded into DEEPSEEK / MIXTRAL)
+  int expert_type = ET_MIXTRAL;  // MOEINF_EXPERT_*
+  int dtype = DT_BF16;           // activations (and the shared expert's weights)
+  int gate_dtype = DT_BF16;
+  int slot_dtype = DT_BF16;      // the routed experts' weights in their HBM slots: `dtype`, DT_F8 or DT_MX4
+  int T = 1, K = 2, E = 8, H = 0, F = 0, Fs = 0;
+  int has_shared = 0;
+  int n_group = 1;
+  int v3 = 0;                    // DeepSeek-V3's gate
+  int capacity = 0;              // Switch per-row expert capacity (IndexArgs::capacity; <= 0: unlimited)
+  int flags = 0;                 // LAYER_ROUTE_ONLY | LAYER_NO_COMBINE
+  int masked = 0;                // the forward has a token mask
+  int fast = 1;                  // sync-free path (MirrorPlan::fast); 0: the decision path
+  int ovr_out = 0;               // stage 2 writes to an override buffer (expert-parallel owner side)
+  int num_cus = 256;
+  int l1_wgs_per_cu = 0;         // workgroups of the Switch one-launch kernel a CU holds (layer1_switch_wgs_per_cu, asked once; 0: unknown)
+};
+
+// decode-sized DeepSeek forwards: the shared expert (routing-independent, always resident) runs INSIDE the two router launches
+// instead of behind them.  The one predicate for it: layer_form and the expert-parallel route (engine_ep.cpp) call it.
+// (fp16 since round 5: gate_shared1 / route_shared2 / moe_front1 on half_t; fp32 experts keep the shared expert behind the router)
+// (the gate is in the model dtype or fp32: moeinf_create refuses the mixed pairs)
+inline bool can_hide_shared(const LayerShape& s, const LayerKnobs& k) {
+  return k.hide_shared && s.has_shared && (s.dtype == DT_BF16 || s.dtype == DT_F16) && s.T <= HIDE_SHARED_MAX_TOKENS && s.T * s.K <= 64 &&
+         s.router_kind == RK_DEEPSEEK;
+}
+
+// the gate's own form: GATE_MFMA = gate_logits_mfma_kernel, else gate_logits_kernel with TT = 1 / 4 tokens per workgroup.
+// The fp64-matrix form from 128 (16-token x 16-expert) tiles on — below that its few workgroups lose to the decode-shaped
+// kernel (measured: DeepSeek-V2-Lite 4096 / 512 / 128 tokens route 207 -> 75, 58 -> 47, 36 -> 39 us; NLLB 2048 tokens
+// 195 -> 71; Mixtral, one padded tile: 4096 tokens 46 -> 30, 512 tokens 27 -> 39).  MOEINF_GATE_MFMA_TILES=0: never.
+// One token (batch-1 decode, the gate launch in front of the self-routing stage 1): ONE cross-lane reduction per workgroup
+// instead of four (the fp64 shuffles of the three absent tokens were most of the kernel: round 5, seen in the timelines of
+// csrc/layer_fused.hip — gate done after 1.6 us instead of 2.6)
+enum { GATE_NONE = 0, GATE_TT1 = 1, GATE_TT4 = 4, GATE_MFMA = 16 };
+inline int gate_form(int T, int E, int H, const LayerKnobs& k) {
+  if (k.gate_mfma_tiles > 0 && (int64_t)((T + 15) / 16) * ((E + 15) / 16) >= k.gate_mfma_tiles && (H & 63) == 0) return GATE_MFMA;
+  return T == 1 ? GATE_TT1 : GATE_TT4;
+}
+// long prefills: the index over many workgroups (one workgroup walks 1024-pair chunks serially, ~12 us each); not with a Switch
+// per-row capacity (a sequential pass).  moe_forward and launch_index_auto share it.
+inline bool index_is_wide(int capacity, int64_t pairs, const LayerKnobs& k) { return capacity <= 0 && pairs > k.index_wide_pairs; }
+
+struct RowsForm { int waves = 0, unroll = 0; };  // of a ffn_rows_item that rides in a router launch
+// gate_shared1: 8 tiles per wave and matrix per batch: 1.035 -> 1.007 ms/token (DeepSeek-V2-Lite).  MOEINF_SH1_NW=8: eight waves per
+// workgroup (a shared-expert work item of 16 rows x 2 matrices x K = 128 KB for DeepSeek-V2-Lite then goes in flight in ONE batch of
+// loads per wave instead of two); round 4: 0.984 -> 0.968 ms/token (A/B/A in one run); 4 = the four-wave form.  fp16 model (round 5):
+// the default eight-wave form only
+inline RowsForm shared1_form(int dtype, const LayerKnobs& k) {
+  if (dtype == DT_F16 || k.sh1_nw == 8) return {8, 8};
+  return {4, k.sh1_u == 8 ? 8 : 4};
+}
+// route_shared2 (fp16: the default form only)
+inline RowsForm shared2_form(int dtype, const LayerKnobs& k) {
+  if (dtype == DT_F16) return {8, 4};
+  return {k.sh2_nw == 16 ? 16 : (k.sh2_nw == 4 ? 4 : 8), k.sh2_u == 8 ? 8 : 4};
+}
+
+// the geometry of a self-routing stage 1, ONE rule for launch_ffn1_selfroute, launch_ffn1_selfroute_multi and launch_moe_front1
+// (the expert-parallel broadcast stage 1, launch_ffn_epb_stage1 in ep_kernels.hip, keeps a copy of its LDS / tiles part: not a layer_form launch)
+enum { ST_NONE = 0, ST_GENERIC = 1, ST_SELFROUTE = 2, ST_SELFROUTE_MULTI = 3, ST_FRONT1 = 4, ST_LAYER1_SWITCH = 5, ST_DECODE1 = 6 };
+struct SelfRouteForm {
+  int waves = 0;       // per workgroup: 4 (gated), 16 (plain experts: Switch)
+  int tiles = 0;       // per wave, matrix and batch: 8 or 4
+  int lds_kb = 0;      // dynamic LDS per workgroup (a cap on the workgroups resident per CU)
+  int shared_last = 0; // the hidden shared expert's work items are dispatched last
+  int grid = 0;
+};
+// launcher: ST_SELFROUTE / ST_SELFROUTE_MULTI / ST_FRONT1; gated: a gated-SiLU stage (else Switch's plain experts);
+// n_rg / n_sh1 / n_sh2: row groups of the routed stage 1 and of the hidden shared expert's stages carried by the launch; slots: K
+// (batch 1) or min(E, T * K) expert slots
+inline SelfRouteForm selfroute_form(int launcher, bool gated, int dtype, int slot_dtype, int E, int slots, int n_rg, int n_sh1, int n_sh2,
+                                    const LayerKnobs& k) {
+  SelfRouteForm f;
+  f.grid = (launcher == ST_FRONT1 ? E + n_sh1 : 0) + 1 + n_sh2 + slots * n_rg;
+  if (!gated) {
+    // plain experts (Switch, top-1): a grid of at most one workgroup per CU gets sixteen waves per workgroup — the whole
+    // work item in flight at once (see ffn_form)
+    f.waves = 16; f.tiles = 4;
+    return f;
+  }
+  // Extra dynamic LDS per workgroup = a cap on the workgroups resident per CU.  A grid of several workgroups per CU
+  // (Mixtral: 1793) streams best with FOUR resident per CU (8 + 30 KB of LDS each), the rest dispatched as they retire:
+  // 3.942 / 3.935 / 3.920 / 3.891 / 3.939 ms per token at 7 / 6 / 5 / 4 / 3 per CU — fewer concurrent DRAM streams,
+  // staggered finishes.  Small grids (DeepSeek: 657 workgroups, all resident anyway) are left alone.
+  // Tiles per wave and matrix fetched per batch: 8 for grids that are resident all at once (DeepSeek-V2-Lite: 657
+  // workgroups, 1.035 -> 1.009 ms/token), 4 for multi-round grids (Mixtral: 1793 workgroups at four per CU).
+  // Kept as it was: the multi-token launcher follows the rule but neither MOEINF_SR_LDS_KB nor MOEINF_SR_U; MOEINF_SR_ORDER is
+  // honoured by the batch-1 launcher with bf16 weights only.
+  const bool multi_round = f.grid > 4 * 256, knobs = launcher != ST_SELFROUTE_MULTI;
+  f.waves = 4;
+  f.lds_kb = knobs && k.sr_lds_kb >= 0 ? k.sr_lds_kb : (multi_round ? 30 : 0);
+  f.tiles = (knobs && k.sr_u ? k.sr_u : (multi_round ? 4 : 8)) == 8 ? 8 : 4;
+  f.shared_last = launcher == ST_SELFROUTE && k.sr_order && n_sh2 > 0 && dtype == DT_BF16 && slot_dtype == DT_BF16;
+  return f;
+}
+
+// the form of launch_ffn2_decode1 (stage 2 of a batch-1 self-routed forward, combine in its tail), ONE rule for bf16 / fp16 / fp32
+// activations and fp8 / MXFP4 slots
+struct Decode1Form {
+  int pair = 0;    // 1: ffn2_decode1_pair_kernel (one workgroup owns 16 output columns for BOTH chosen experts), 0: the arrival-counter form
+  int waves = 0;   // pair: per expert (the workgroup has twice as many); counter: per workgroup
+  int unroll = 0;  // k-tiles per wave fetched per batch
+  int grid_x = 0, grid_y = 0;
+};
+constexpr int DEC1_LONG_ROW_BYTES = 16384;  // a weight row of this many bytes gets eight waves per workgroup in the arrival-counter form
+// kind: router kind (the combine's semantics); top_k = the token's experts; K / R: stage 2's reduction length / output rows;
+// shared: the combine adds a shared expert's row
+inline Decode1Form decode1_form(int dtype, int slot_dtype, int kind, int top_k, int K, int R, bool shared, const LayerKnobs& k) {
+  Decode1Form f;
+  const bool slot = slot_dtype == DT_F8 || slot_dtype == DT_MX4, b16 = dtype == DT_BF16 && !slot;
+  f.grid_x = (R + 15) / 16;
+  // K = 2 (Mixtral): 4 waves per expert (8 per CU), batches of 4 tiles: 38.9 us per Mixtral launch; 8 waves per expert 40.5; the
+  // arrival-counter form 41.9.  Kept as it was: fp16 takes the default pair form only; MOEINF_DEC1_PAIR=8 and _PAIR_U=2 are bf16's.
+  if (k.dec1_pair && top_k == 2 && kind <= RK_DEEPSEEK && !(kind == RK_DEEPSEEK && shared) &&
+      (slot || ((dtype == DT_BF16 || dtype == DT_F16) && K % 32 == 0))) {
+    f.pair = 1; f.grid_y = 1; f.waves = 4; f.unroll = 4;
+    if (b16 && k.dec1_pair == 8) f.waves = 8;
+    else if ((b16 || slot) && k.dec1_pair_u == 8) f.unroll = 8;
+    else if (b16 && k.dec1_pair_u == 2) f.unroll = 2;
+    return f;
+  }
+  // (K = 3..8 — DeepSeek: six routed experts + the hidden shared expert — keeps the arrival-counter form.  ONE workgroup per column
+  // block with every chosen expert and the combine inside it was built twice: on half tiles, eight columns, 256 workgroups (round 3)
+  // and on whole tiles, 128 workgroups of twelve waves (round 6); both measured slower than the tail they remove — 33.3 / 33.0-33.5
+  // against 32.5 us per DeepSeek-V2-Lite layer, profiles/r06_deepseek_stage2_group_forms_rejected.txt — and both are deleted.)
+  f.grid_y = top_k;
+  if (kind == RK_SWITCH) {
+    // Switch, top-1: H/16 workgroups (48 for Switch-base) of sixteen waves.  Twelve tiles per wave and batch: Switch-base's down
+    // projection is 192 tiles per row group = 16 waves x 12, i.e. the workgroup's whole 197 KB in flight at once
+    // (MOEINF_DEC1_SWITCH_U=4: three batches of four, 10.6 us per launch)
+    f.waves = 16; f.unroll = k.dec1_switch_u == 12 ? 12 : 4;
+    return f;
+  }
+  // by weight bytes per row: long reductions get eight waves per workgroup, short ones four and MOEINF_DEC1_U tiles per batch
+  // (kept as it was: 12 is bf16's, fp16 takes 4 only)
+  const int64_t row_bytes = slot_dtype == DT_MX4 ? K / 2 : (slot_dtype == DT_F8 ? K : (int64_t)K * 2);
+  if (row_bytes >= DEC1_LONG_ROW_BYTES) { f.waves = 8; f.unroll = 4; return f; }
+  f.waves = 4; f.unroll = 4;
+  if ((b16 || slot) && k.dec1_u == 8) f.unroll = 8;
+  else if (b16 && k.dec1_u == 12) f.unroll = 12;
+  return f;
+}
+
+// what launch_moe_layer1_switch takes: x and experts in one dtype (fp32 for Switch-base, bf16), gate in the model dtype or fp32, every
+// workgroup resident at once (what the chip HOLDS is asked — wgs_per_cu, an occupancy query —, not assumed; at most two per CU even
+// if more fit), a reduction the four-way split covers.  R1 x K1 / R2 x K2: the two stages' matrices
+inline bool layer1_switch_fits(int dtype, int gate_dtype, int slot_dtype, int E, int top_k, int R1, int K1, int R2, int K2, int num_cus,
+                               int wgs_per_cu) {
+  constexpr int KS = 4, P2 = 6, NW = 8;
+  const int grid = E + 1 + (R1 + 15) / 16 + KS * ((R2 + 15) / 16), ept = dtype == DT_F32 ? 16 : 32;
+  const int per_cu = wgs_per_cu > 0 ? (wgs_per_cu < 2 ? wgs_per_cu : 2) : 0;
+  if (slot_dtype == DT_F8 || slot_dtype == DT_MX4 || dtype == DT_F16 || top_k != 1) return false;
+  if (per_cu == 0 || grid > per_cu * num_cus || K2 % (ept * KS) != 0 || K1 % ept != 0 || K2 / ept / KS > NW * P2) return false;
+  return dtype == DT_F32 ? gate_dtype == DT_F32 : (gate_dtype == DT_BF16 || gate_dtype == DT_F32);
+}
+
+// the router launches of a forward
+enum {
+  ROUTER_NONE = 0,              // nothing here: stage 1's launch carries the gate (front1, the Switch one-launch layer)
+  ROUTER_GATE = 1,              // the gate; stage 1 routes for itself
+  ROUTER_GATE_SHARED1 = 2,      // ... with the hidden shared expert's stage 1 in the gate launch
+  ROUTER_GATE_SHARED1_ROUTE_SHARED2 = 3,  // gate + shared stage 1, then top-k + index + shared stage 2
+  ROUTER_GATE_ROUTE_INDEX = 4,  // gate, then top-k + dispatch index in one launch (up to 64 tokens)
+  ROUTER_GATE_TOPK_INDEX = 5,   // gate, top-k, the one-workgroup index
+  ROUTER_GATE_TOPK_WIDE = 6     // gate, top-k, the many-workgroup index (three launches)
+};
+enum { SR_NONE = 0, SR_BATCH1 = 1, SR_MULTI = 2 };
+enum { L1_NO = 0, L1_ONE_LAUNCH = 1, L1_DECLINED = 2 };  // declined: chosen, but the launcher does not take the shape — the three launches
+struct LayerForm {
+  int hide_shared = 0;
+  int selfroute = SR_NONE;
+  int front1 = 0;
+  int layer1_switch = L1_NO;
+  int router = ROUTER_GATE_ROUTE_INDEX;
+  int gate = GATE_NONE;        // form of a gate launch of its own (GATE_NONE: the gate rides in another launch; gate_shared1 is TT = 4)
+  int stage1 = ST_GENERIC;     // ST_NONE (route only) | ST_GENERIC (launch_ffn_stage: ffn_form) | ST_SELFROUTE | ST_SELFROUTE_MULTI | ST_FRONT1 | ST_LAYER1_SWITCH
+  SelfRouteForm sr;            // ST_SELFROUTE / _MULTI / ST_FRONT1
+  int stage2 = ST_GENERIC;     // ST_NONE (route only, inside the one-launch layer) | ST_GENERIC | ST_DECODE1
+  Decode1Form dec1;            // ST_DECODE1
+  RowsForm shared1, shared2;   // gate_shared1 / route_shared2, where the router launches them
+  int can_fuse_combine = 0;    // stage 2 may carry the combine in its epilogue (decision path: when the layer runs as one chunk)
+  int fuse_mode = 1;           // FfnStage::fuse_combine of such a stage 2
+  int kt1 = 1;                 // stage 1 is ONE launch and carries the profiling timer on its own dispatch packet
+  int poll_sleep = 0;          // ST_FRONT1 / ST_LAYER1_SWITCH: s_sleep(2) repetitions between two polls of a counter (LayerSync::sleep)
+};
+inline LayerForm layer_form(const LayerShape& s, const LayerKnobs& k) {
+  LayerForm f;
+  const int T = s.T, K = s.K, E = s.E;
+  const bool route_only = s.flags & LAYER_ROUTE_ONLY, no_combine = s.flags & LAYER_NO_COMBINE;
+  const bool hide = !route_only && can_hide_shared(s, k);
+  f.hide_shared = hide;
+  // batch-1 decode on the sync-free path (gated families, bf16): no top-k/index launch at all — FFN stage 1 routes for
+  // itself from the gate logits (ffn1_selfroute_kernel) and one extra block of it writes the routing outputs
+  const bool sr_gated = s.dtype != DT_F32 &&
+                        (s.router_kind == RK_MIXTRAL || (s.router_kind == RK_DEEPSEEK && s.n_group <= 1 && !s.v3)) &&
+                        (s.expert_type == ET_MIXTRAL || s.expert_type == ET_DEEPSEEK) && (!s.has_shared || hide);
+  // (round 4) Switch: top-1, plain ReLU experts, bf16 or fp32; a single token can never exceed the per-row capacity
+  const bool sr_switch = s.router_kind == RK_SWITCH && s.expert_type == ET_SWITCH && K == 1 && !s.has_shared && !no_combine && s.capacity != 0;
+  // (round 4) decode batches of 2..8 tokens of the gated families: the same idea, every workgroup routes every token
+  // Measured (profiles/r04_small_batch_selfroute.txt): DeepSeek-V2-Lite batch 2 / 4: 1.530 -> 1.373 / 2.163 -> 2.056 ms per step;
+  // batch 8 (48 pairs over 64 experts): 3.17 -> 3.61 — every workgroup of the worst-case grid (48 expert slots) pays eight
+  // routings before it knows that its slot is empty.  Hence at most 24 (token, expert) pairs; Mixtral (8 experts, all of them
+  // active from batch 4 on) gains 2.3 / 0.9 / 0.6 % at batch 2 / 4 / 8.
+  const bool sr_multi = T >= 2 && T <= (k.selfroute_multi < 8 ? k.selfroute_multi : 8) &&
+                        T * K <= (k.selfroute_multi_pairs < 64 ? k.selfroute_multi_pairs : 64) && sr_gated;
+  // A token mask takes the generic router launches (route_core reads the mask): the self-routing forms (selfroute, multi,
+  // moe_front1, the Switch one-launch layer) and the fused combine assume every token keeps its K experts, so stage 2 always runs.
+  const bool selfroute = k.selfroute && !s.masked && !route_only && s.fast && K <= 8 && E <= 64 && !s.ovr_out &&
+                         ((T == 1 && (sr_gated || sr_switch)) || sr_multi);
+  f.selfroute = !selfroute ? SR_NONE : (T == 1 ? SR_BATCH1 : SR_MULTI);
+  // decode-sized Mixtral/DeepSeek forwards (every token keeps K experts, so stage 2 always runs): the combine
+  // rides in the epilogue of FFN stage 2.  (Switch: only the batch-1 stage 2 knows its combine)
+  f.can_fuse_combine = !route_only && k.fuse_combine && !no_combine && T <= 16 && !s.masked &&
+                       (s.router_kind == RK_MIXTRAL || s.router_kind == RK_DEEPSEEK || (selfroute && sr_switch));
+  // FfnStage::fuse_combine: 1 = the hand-off rows leave as sixteen 2-byte write-through stores; 2 (MOEINF_WIDE_OUT=1) = gathered
+  // through LDS into 16-byte ones — measured SLOWER (DeepSeek-V2-Lite 1.031/1.038 vs 1.022/1.031 ms/token, stage 2 +0.6 us: the
+  // extra LDS round trip and barrier cost more than the fabric writes they save), so off by default
+  f.fuse_mode = k.wide_out ? 2 : 1;
+  // (the whole DeepSeek layer as ONE persistent launch was built in round 5, measured slower — 1.09 vs 0.958 ms/token — and
+  // removed in round 6: DESIGN.md section 4.5.1 keeps the analysis)
+  // Switch (top-1, no shared expert): the one-launch form is the DEFAULT — three launches of 3-10 us for 18.9 MB are pure fixed
+  // cost, and with hardly any traffic in flight a flag costs ~1 us (MOEINF_LAYER1_SWITCH=0: the three launches)
+  if (k.layer1_switch && selfroute && T == 1 && sr_switch && !sr_gated && !no_combine && s.dtype != DT_F16)
+    f.layer1_switch = f.can_fuse_combine && layer1_switch_fits(s.dtype, s.gate_dtype, s.slot_dtype, E, K, s.F, s.H, s.H, s.F, s.num_cus, s.l1_wgs_per_cu)
+                          ? L1_ONE_LAUNCH : L1_DECLINED;
+  // the gated families: the gate (and the hidden shared expert) can ride in FRONT of the self-routing stage 1, in the same
+  // launch (round 5, launch_moe_front1).  Measured A/B/A/B (profiles/r05_front1_gate_and_stage1_in_one_launch.txt): DeepSeek-V2-Lite
+  // 0.949-0.967 -> 0.937 ms/token (two launches per layer instead of three) = the default with a hidden shared expert; Mixtral
+  // 3.708-3.726 -> 3.723-3.728 (nothing: the hop costs what the gate launch cost) = off unless MOEINF_FRONT1=1; =0: never
+  f.front1 = (k.front1 < 0 ? hide : k.front1 != 0) && selfroute && T == 1 && sr_gated && s.dtype != DT_F32 && (hide || !s.has_shared) &&
+             (s.gate_dtype == s.dtype || s.gate_dtype == DT_F32);
+  const bool one_launch = f.layer1_switch == L1_ONE_LAUNCH;
+  if (one_launch || f.front1) f.router = ROUTER_NONE;
+  else if (selfroute) f.router = hide ? ROUTER_GATE_SHARED1 : ROUTER_GATE;
+  else if (hide) f.router = ROUTER_GATE_SHARED1_ROUTE_SHARED2;
+  else if (T <= 64) f.router = ROUTER_GATE_ROUTE_INDEX;  // decode: top-k + dispatch index in one launch
+  else f.router = index_is_wide(s.capacity, (int64_t)T * K, k) ? ROUTER_GATE_TOPK_WIDE : ROUTER_GATE_TOPK_INDEX;
+  if (f.router == ROUTER_GATE_SHARED1 || f.router == ROUTER_GATE_SHARED1_ROUTE_SHARED2) f.shared1 = shared1_form(s.dtype, k);
+  else if (f.router != ROUTER_NONE) f.gate = gate_form(T, E, s.H, k);
+  if (f.router == ROUTER_GATE_SHARED1_ROUTE_SHARED2) f.shared2 = shared2_form(s.dtype, k);
+  if (route_only) { f.stage1 = f.stage2 = ST_NONE; return f; }
+  f.stage1 = one_launch ? ST_LAYER1_SWITCH : (f.front1 ? ST_FRONT1 : (!selfroute ? ST_GENERIC : (T > 1 ? ST_SELFROUTE_MULTI : ST_SELFROUTE)));
+  if (f.stage1 == ST_SELFROUTE || f.stage1 == ST_SELFROUTE_MULTI || f.stage1 == ST_FRONT1)
+    f.sr = selfroute_form(f.stage1, !sr_switch, s.dtype, s.slot_dtype, E, T == 1 ? K : (E < T * K ? E : T * K), (s.F + 15) / 16,
+                          hide && f.front1 ? (s.Fs + 15) / 16 : 0, hide ? (s.H + 15) / 16 : 0, k);
+  f.stage2 = one_launch ? ST_NONE : (selfroute && f.can_fuse_combine && T == 1 ? ST_DECODE1 : ST_GENERIC);
+  if (f.stage2 == ST_DECODE1) f.dec1 = decode1_form(s.dtype, s.slot_dtype, s.router_kind, K, s.F, s.H, s.has_shared != 0, k);
+  // decode launchers that carry the timer on their own dispatch packet: no event-record packets inside the interval
+  // (every FFN-stage launcher is ONE launch and carries the timer; the small-batch self-routing stage 1 is the exception)
+  f.kt1 = f.stage1 != ST_SELFROUTE_MULTI;
+  if (f.stage1 == ST_FRONT1 || f.stage1 == ST_LAYER1_SWITCH) f.poll_sleep = k.layer1_sleep;
+  return f;
+}
+
 // max_rows_per_expert: upper bound of rows any one expert receives (selects the kernel and its form); num_cus: of the device
 hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st);
 // the grouped GEMMs, one launcher per translation unit: each maps the form ffn_form chose to its instantiation
@@ -447,14 +760,14 @@ hipError_t launch_route_shared2(const RouteArgs& r, const IndexArgs& a, const Ff
 void arm_kernel_timer(hipEvent_t start, hipEvent_t stop);
 bool take_kernel_timer(hipEvent_t* start, hipEvent_t* stop);
 inline void disarm_kernel_timer() { hipEvent_t a, b; (void)take_kernel_timer(&a, &b); }  // after a launch that may have failed before taking it
-hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, hipStream_t st);
+hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, const SelfRouteForm& f, hipStream_t st);
 // The same for decode batches of 2..8 tokens (bf16 / fp16 gated families, T*K <= 64): the meta block routes every token and
 // builds the index, every other workgroup routes the tokens for itself; stage 2 is the generic launch_ffn_stage (combine fused).
-// max_active = min(E, T*K).
-hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, int max_active, hipStream_t st);
+// max_active = min(E, T*K).  f (here and above, and for launch_moe_front1): the geometry selfroute_form chose.
+hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, int max_active, const SelfRouteForm& f, hipStream_t st);
 // ... and its stage 2 (s2.fuse_combine set, K = s2.comb.K active experts, one token): blob pointers and combine weights
-// come from the records the self-routing launch left in s2.dec_w / s2.dec_cw
-hipError_t launch_ffn2_decode1(const FfnStage& s2, hipStream_t st);
+// come from the records the self-routing launch left in s2.dec_w / s2.dec_cw; f: the form decode1_form chose
+hipError_t launch_ffn2_decode1(const FfnStage& s2, const Decode1Form& f, hipStream_t st);
 // A whole batch-1 decode layer (gated family, hidden shared expert) in ONE launch (layer_fused.hip): gate | shared stage 1 |
 // meta | self-routing stage 1 | shared stage 2 | stage 2 + combine as workgroups of one grid; what used to be a kernel boundary
 // is a counter that only grows.  ctr: LAYER1_CTRS words, LAYER1_CTR_STRIDE apart (one cache line each), zeroed once; launch =
@@ -473,9 +786,9 @@ struct LayerSync {
 };
 // the FRONT of a batch-1 layer of the gated families in one launch: gate | (shared stage 1) | meta | self-routing stage 1 |
 // (shared stage 2); stage 2 + combine stay launch_ffn2_decode1.  sh1 / sh2: the hidden shared expert's stages or nullptr.
-hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnStage* sh1, const FfnStage* sh2, const FfnStage& s1, const LayerSync& sy, hipStream_t st);
+hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnStage* sh1, const FfnStage* sh2, const FfnStage& s1, const LayerSync& sy, const SelfRouteForm& f, hipStream_t st);
 // the Switch form (top-1, plain experts, no shared expert): E + 1 + F/16 + 4 * H/16 workgroups of eight waves, all resident at once;
-// false: not handled (the caller runs the three launches)
+// false: not handled (layer1_switch_fits says so beforehand: layer_form then plans the three launches)
 bool launch_moe_layer1_switch(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage& s2, const LayerSync& sy, int num_cus, int wgs_per_cu, hipStream_t st);
 // workgroups of that kernel one CU holds at a time (hipOccupancyMaxActiveBlocksPerMultiprocessor of the instantiation; 0: unknown)
 int layer1_switch_wgs_per_cu(int x_dtype, int gate_dtype);

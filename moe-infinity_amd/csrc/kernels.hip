@@ -495,23 +495,15 @@ hipError_t launch_gate_shared1(const RouteArgs& a, const FfnStage& s, hipStream_
   const int n_gate = a.E * ((a.T + TT - 1) / TT);
   dim3 grid(n_gate + (s.R_sh + 15) / 16);
   const int rb = gate_rounds_bf16(a);
-  // bf16 model (DeepSeek): activations bf16, gate bf16 or fp32
-  static const int u8 = env_int("MOEINF_SH1_U", 8) == 8;  // 8 tiles per wave and matrix per batch: 1.035 -> 1.007 ms/token (DeepSeek-V2-Lite)
-  // MOEINF_SH1_NW=8: eight waves per workgroup (a shared-expert work item of 16 rows x 2 matrices x K = 128 KB for
-  // DeepSeek-V2-Lite then goes in flight in ONE batch of loads per wave instead of two)
-  static const int nw8 = env_int("MOEINF_SH1_NW", 8) == 8;  // round 4: 0.984 -> 0.968 ms/token (A/B/A in one run); 4 = the four-wave form
-#define GS1(WT, UU) hipLaunchKernelGGL((gate_shared1_kernel<uint16_t, WT, TT, uint16_t, UU>), grid, dim3(256), 0, st, (const uint16_t*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb, n_gate, s)
-#define GS8(WT, UU) hipLaunchKernelGGL((gate_shared1_kernel<uint16_t, WT, TT, uint16_t, UU, 8>), grid, dim3(512), 0, st, (const uint16_t*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb, n_gate, s)
-  if (a.x_dtype == DT_F16) {  // fp16 model (round 5): the default eight-wave form only, gate fp16 or fp32
-    if (a.gate_dtype == DT_F16) hipLaunchKernelGGL((gate_shared1_kernel<half_t, half_t, TT, half_t, 8, 8>), grid, dim3(512), 0, st, (const half_t*)a.x, (const half_t*)a.gate_w, a.logits, a.T, a.H, a.E, rb, n_gate, s);
-    else if (a.gate_dtype == DT_F32) hipLaunchKernelGGL((gate_shared1_kernel<half_t, float, TT, half_t, 8, 8>), grid, dim3(512), 0, st, (const half_t*)a.x, (const float*)a.gate_w, a.logits, a.T, a.H, a.E, rb, n_gate, s);
-    else return hipErrorInvalidValue;
-  } else if (nw8) {
-    if (a.gate_dtype == DT_BF16) GS8(uint16_t, 8); else GS8(float, 8);
-  } else if (a.gate_dtype == DT_BF16) { if (u8) GS1(uint16_t, 8); else GS1(uint16_t, 4); }
-  else { if (u8) GS1(float, 8); else GS1(float, 4); }
-#undef GS1
-#undef GS8
+  const RowsForm f = shared1_form(a.x_dtype, layer_knobs());
+#define GS(XT, WT, UU, NWV) hipLaunchKernelGGL((gate_shared1_kernel<XT, WT, TT, XT, UU, NWV>), grid, dim3(NWV * 64), 0, st, (const XT*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb, n_gate, s)
+  if (a.x_dtype == DT_F16) {  // fp16 model (round 5): gate fp16 or fp32
+    if (a.gate_dtype == DT_F16) GS(half_t, half_t, 8, 8); else if (a.gate_dtype == DT_F32) GS(half_t, float, 8, 8); else return hipErrorInvalidValue;
+  } else if (f.waves == 8) {  // bf16 model (DeepSeek): activations bf16, gate bf16 or fp32
+    if (a.gate_dtype == DT_BF16) GS(uint16_t, uint16_t, 8, 8); else GS(uint16_t, float, 8, 8);
+  } else if (a.gate_dtype == DT_BF16) { if (f.unroll == 8) GS(uint16_t, uint16_t, 8, 4); else GS(uint16_t, uint16_t, 4, 4); }
+  else { if (f.unroll == 8) GS(uint16_t, float, 8, 4); else GS(uint16_t, float, 4, 4); }
+#undef GS
   return hipGetLastError();
 }
 
@@ -568,34 +560,21 @@ __global__ __launch_bounds__(256) void gate_logits_mfma_kernel(const XT* __restr
 
 hipError_t launch_gate_logits(const RouteArgs& a, hipStream_t st) {
   constexpr int TT = 4;
-  dim3 grid(a.E, (a.T + TT - 1) / TT);
   const int rb = gate_rounds_bf16(a);
-  // the fp64-matrix form from 128 (16-token x 16-expert) tiles on — below that its few workgroups lose to the decode-shaped
-  // kernel (measured: DeepSeek-V2-Lite 4096 / 512 / 128 tokens route 207 -> 75, 58 -> 47, 36 -> 39 us; NLLB 2048 tokens
-  // 195 -> 71; Mixtral, one padded tile: 4096 tokens 46 -> 30, 512 tokens 27 -> 39).  MOEINF_GATE_MFMA_TILES=0: never
-  static const int mfma_tiles = env_int("MOEINF_GATE_MFMA_TILES", 128);
-  if (mfma_tiles > 0 && (int64_t)((a.T + 15) / 16) * ((a.E + 15) / 16) >= mfma_tiles && (a.H & 63) == 0) {
-    const dim3 g16((a.T + 15) / 16, (a.E + 15) / 16);
-#define GM(XT, WT) hipLaunchKernelGGL((gate_logits_mfma_kernel<XT, WT>), g16, dim3(256), 0, st, (const XT*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb)
-    if (a.x_dtype == DT_F16) { if (a.gate_dtype == DT_F16) GM(half_t, half_t); else GM(half_t, float); }
-    else if (a.x_dtype == DT_BF16 && a.gate_dtype == DT_BF16) GM(uint16_t, uint16_t);
-    else if (a.x_dtype == DT_BF16) GM(uint16_t, float);
-    else if (a.gate_dtype == DT_BF16) GM(float, uint16_t);
-    else GM(float, float);
-#undef GM
-    return hipGetLastError();
-  }
-  // one token (batch-1 decode, the gate launch in front of the self-routing stage 1): ONE cross-lane reduction per workgroup
-  // instead of four (the fp64 shuffles of the three absent tokens were most of the kernel: round 5, seen in the timelines of
-  // csrc/layer_fused.hip — gate done after 1.6 us instead of 2.6)
-#define GL(XT, WT) do { if (a.T == 1) hipLaunchKernelGGL((gate_logits_kernel<XT, WT, 1>), grid, dim3(256), 0, st, (const XT*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb); \
-                        else hipLaunchKernelGGL((gate_logits_kernel<XT, WT, TT>), grid, dim3(256), 0, st, (const XT*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb); } while (0)
+  const int form = gate_form(a.T, a.E, a.H, layer_knobs());
+  const dim3 grid = form == GATE_MFMA ? dim3((a.T + 15) / 16, (a.E + 15) / 16) : dim3(a.E, (a.T + TT - 1) / TT);
+#define GA (const XT*)a.x, (const WT*)a.gate_w, a.logits, a.T, a.H, a.E, rb
+#define GL(XT_, WT_) do { using XT = XT_; using WT = WT_; \
+    if (form == GATE_MFMA) hipLaunchKernelGGL((gate_logits_mfma_kernel<XT, WT>), grid, dim3(256), 0, st, GA); \
+    else if (form == GATE_TT1) hipLaunchKernelGGL((gate_logits_kernel<XT, WT, 1>), grid, dim3(256), 0, st, GA); \
+    else hipLaunchKernelGGL((gate_logits_kernel<XT, WT, TT>), grid, dim3(256), 0, st, GA); } while (0)
   if (a.x_dtype == DT_F16) { if (a.gate_dtype == DT_F16) GL(half_t, half_t); else GL(half_t, float); }
   else if (a.x_dtype == DT_BF16 && a.gate_dtype == DT_BF16) GL(uint16_t, uint16_t);
   else if (a.x_dtype == DT_BF16) GL(uint16_t, float);
   else if (a.gate_dtype == DT_BF16) GL(float, uint16_t);
   else GL(float, float);
 #undef GL
+#undef GA
   return hipGetLastError();
 }
 
@@ -767,14 +746,14 @@ static EpFuse no_pack() {
   return f;
 }
 hipError_t launch_route_shared2(const RouteArgs& r, const IndexArgs& a, const FfnStage& s, hipStream_t st, const EpFuse* pack) {
-  static const int nw = env_int("MOEINF_SH2_NW", 8), u = env_int("MOEINF_SH2_U", 4);
+  const RowsForm f = shared2_form(s.dtype, layer_knobs());
   const dim3 grid(1 + (s.R_sh + 15) / 16);
   const EpFuse pk = pack ? *pack : no_pack();
 #define RS2(NWV, UU) hipLaunchKernelGGL((route_shared2_kernel<uint16_t, NWV, UU>), grid, dim3(NWV * 64), 0, st, r, a, s, pk)
-  if (s.dtype == DT_F16) hipLaunchKernelGGL((route_shared2_kernel<half_t, 8, 4>), grid, dim3(512), 0, st, r, a, s, pk);  // fp16: the default form only
-  else if (nw == 16) { if (u == 8) RS2(16, 8); else RS2(16, 4); }
-  else if (nw == 4) { if (u == 8) RS2(4, 8); else RS2(4, 4); }
-  else { if (u == 8) RS2(8, 8); else RS2(8, 4); }
+  if (s.dtype == DT_F16) hipLaunchKernelGGL((route_shared2_kernel<half_t, 8, 4>), grid, dim3(512), 0, st, r, a, s, pk);
+  else if (f.waves == 16) { if (f.unroll == 8) RS2(16, 8); else RS2(16, 4); }
+  else if (f.waves == 4) { if (f.unroll == 8) RS2(4, 8); else RS2(4, 4); }
+  else { if (f.unroll == 8) RS2(8, 8); else RS2(8, 4); }
 #undef RS2
   return hipGetLastError();
 }
@@ -879,50 +858,28 @@ bool take_kernel_timer(hipEvent_t* start, hipEvent_t* stop) {
   t_timer_start = t_timer_stop = nullptr;
   return true;
 }
-hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, hipStream_t st) {
+hipError_t launch_ffn1_selfroute(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, const SelfRouteForm& f, hipStream_t st) {
   const int n_rg = (s1.R + 15) / 16;
   const int n_sh2 = sh2 ? (sh2->R_sh + 15) / 16 : 0;
-  const dim3 grid(n_sh2 + r.K * n_rg + 1);
-  // Extra dynamic LDS per workgroup = a cap on the workgroups resident per CU.  A grid of several workgroups per CU
-  // (Mixtral: 1793) streams best with FOUR resident per CU (8 + 30 KB of LDS each), the rest dispatched as they retire:
-  // 3.942 / 3.935 / 3.920 / 3.891 / 3.939 ms per token at 7 / 6 / 5 / 4 / 3 per CU — fewer concurrent DRAM streams,
-  // staggered finishes.  Small grids (DeepSeek: 657 workgroups, all resident anyway) are left alone.
-  static const int lds_env = env_int("MOEINF_SR_LDS_KB", -1);
-  const size_t dyn = (size_t)(lds_env >= 0 ? lds_env : (grid.x > 4 * 256 ? 30 : 0)) * 1024;
-  // tiles per wave and matrix fetched per batch: 8 for grids that are resident all at once (DeepSeek-V2-Lite: 657
-  // workgroups, 1.035 -> 1.009 ms/token), 4 for multi-round grids (Mixtral: 1793 workgroups at four per CU)
-  static const int sr_u_env = env_int("MOEINF_SR_U", 0);
-  const int sr_u = sr_u_env ? sr_u_env : (grid.x > 4 * 256 ? 4 : 8);
-  if (s1.wdtype == DT_F8) {  // fp8 slots (gated families, bf16)
-    if (s1.epi != EPI_GATED_SILU || s1.dtype != DT_BF16) return hipErrorInvalidValue;
-    if (sr_u == 8) KL((ffn1_selfroute_kernel<f8w_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    else KL((ffn1_selfroute_kernel<f8w_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    return hipGetLastError();
-  }
-  if (s1.wdtype == DT_MX4) {  // MXFP4 slots (gated families, bf16)
-    if (s1.epi != EPI_GATED_SILU || s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
-    if (sr_u == 8) KL((ffn1_selfroute_kernel<mx4w_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    else KL((ffn1_selfroute_kernel<mx4w_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    return hipGetLastError();
-  }
-  if (s1.epi != EPI_GATED_SILU) {
-    // plain experts (Switch, top-1): a grid of at most one workgroup per CU gets sixteen waves per workgroup — the whole
-    // work item in flight at once (see launch_ffn_stage)
-    if (s1.dtype == DT_BF16) KL((ffn1_selfroute_kernel<uint16_t, 1, 16, 4>), grid, dim3(1024), 0, st, r, a, s1, s1, n_rg, 0);
-    else if (s1.dtype == DT_F16) KL((ffn1_selfroute_kernel<half_t, 1, 16, 4>), grid, dim3(1024), 0, st, r, a, s1, s1, n_rg, 0);
-    else KL((ffn1_selfroute_kernel<float, 1, 16, 4>), grid, dim3(1024), 0, st, r, a, s1, s1, n_rg, 0);
-    return hipGetLastError();
-  }
-  if (s1.dtype == DT_F16) {  // fp16 gated families: the same kernel on the f16 matrix instruction
-    if (sr_u == 8) KL((ffn1_selfroute_kernel<half_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    else KL((ffn1_selfroute_kernel<half_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
-    return hipGetLastError();
-  }
-  static const int sr_order = env_int("MOEINF_SR_ORDER", 0);
-  const int n_sh2_arg = (sr_order && n_sh2 > 0) ? -n_sh2 : n_sh2;
-  if (sr_u == 8) KL((ffn1_selfroute_kernel<uint16_t, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2_arg);
-  else KL((ffn1_selfroute_kernel<uint16_t, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2_arg);
-  return hipGetLastError();
+  const bool slot = s1.wdtype == DT_F8 || s1.wdtype == DT_MX4;
+  if (slot && (s1.epi != EPI_GATED_SILU || s1.dtype != DT_BF16 || (s1.wdtype == DT_MX4 && (s1.K % 128) != 0))) return hipErrorInvalidValue;
+  if (f.grid != n_sh2 + r.K * n_rg + 1 || (f.waves == 16) != (s1.epi != EPI_GATED_SILU)) return hipErrorInvalidValue;
+  const dim3 grid(f.grid);
+  const size_t dyn = (size_t)f.lds_kb * 1024;
+  const bool ok = with_kernel_type(s1.dtype, s1.wdtype, [&](auto t) {
+    using T = decltype(t);
+    if (f.waves == 16) {  // plain experts (Switch, top-1)
+      if constexpr (std::is_same<T, f8w_t>::value || std::is_same<T, mx4w_t>::value) return false;
+      else KL((ffn1_selfroute_kernel<T, 1, 16, 4>), grid, dim3(1024), 0, st, r, a, s1, s1, n_rg, 0);
+    } else if constexpr (std::is_same<T, float>::value) return false;
+    else {
+      const int n_sh2_arg = f.shared_last ? -n_sh2 : n_sh2;  // (n_sh2 < 0: the shared expert's work items are dispatched last)
+      if (f.tiles == 8) KL((ffn1_selfroute_kernel<T, 2, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2_arg);
+      else KL((ffn1_selfroute_kernel<T, 2, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2_arg);
+    }
+    return true;
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1007,24 +964,24 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_num_sgpr(96))) void 
   ffn_rows_item<A, 2, NW, U, 1, false, false, T>(s, rg, W, false, cnt, s_off, red, -1, s_in, nullptr);
 }
 
-hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, int max_active, hipStream_t st) {
+hipError_t launch_ffn1_selfroute_multi(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage* sh2, int max_active, const SelfRouteForm& f, hipStream_t st) {
   const int n_rg = (s1.R + 15) / 16;
   const int n_sh2 = sh2 ? (sh2->R_sh + 15) / 16 : 0;
-  const dim3 grid(1 + n_sh2 + max_active * n_rg);
-  const size_t dyn = grid.x > 4 * 256 ? 30 * 1024 : 0;  // as launch_ffn1_selfroute
-#define SRM(TT, UU) hipLaunchKernelGGL((ffn1_selfroute_multi_kernel<TT, 4, UU>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2)
-  if (s1.wdtype == DT_F8) {  // fp8 slots (bf16)
-    if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
-    if (grid.x > 4 * 256) SRM(f8w_t, 4); else SRM(f8w_t, 8);
-  }
-  else if (s1.wdtype == DT_MX4) {  // MXFP4 slots (bf16)
-    if (s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
-    if (grid.x > 4 * 256) SRM(mx4w_t, 4); else SRM(mx4w_t, 8);
-  }
-  else if (s1.dtype == DT_F16) { if (grid.x > 4 * 256) SRM(half_t, 4); else SRM(half_t, 8); }
-  else { if (grid.x > 4 * 256) SRM(uint16_t, 4); else SRM(uint16_t, 8); }
-#undef SRM
-  return hipGetLastError();
+  const bool slot = s1.wdtype == DT_F8 || s1.wdtype == DT_MX4;
+  if (slot && (s1.dtype != DT_BF16 || (s1.wdtype == DT_MX4 && (s1.K % 128) != 0))) return hipErrorInvalidValue;
+  if (f.grid != 1 + n_sh2 + max_active * n_rg) return hipErrorInvalidValue;
+  const dim3 grid(f.grid);
+  const size_t dyn = (size_t)f.lds_kb * 1024;
+  const bool ok = with_kernel_type(s1.dtype, s1.wdtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (std::is_same<T, float>::value) return false;
+    else {
+      if (f.tiles == 8) hipLaunchKernelGGL((ffn1_selfroute_multi_kernel<T, 4, 8>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+      else hipLaunchKernelGGL((ffn1_selfroute_multi_kernel<T, 4, 4>), grid, dim3(256), dyn, st, r, a, s1, sh2 ? *sh2 : s1, n_rg, n_sh2);
+      return true;
+    }
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // Stage 2 of a batch-1 self-routed forward, with the combine in its tail.  Differences from ffn_rows_kernel's fused
@@ -1190,84 +1147,30 @@ __global__ __launch_bounds__(2 * NWE * 64) void ffn2_decode1_pair_kernel(FfnStag
   }
 }
 
-// (K = 3..8 — DeepSeek: six routed experts + the hidden shared expert — keeps the arrival-counter form.  ONE workgroup per column
-// block with every chosen expert and the combine inside it was built twice: on half tiles, eight columns, 256 workgroups (round 3)
-// and on whole tiles, 128 workgroups of twelve waves (round 6); both measured slower than the tail they remove — 33.3 / 33.0-33.5
-// against 32.5 us per DeepSeek-V2-Lite layer, profiles/r06_deepseek_stage2_group_forms_rejected.txt — and both are deleted.)
-hipError_t launch_ffn2_decode1(const FfnStage& s2, hipStream_t st) {
-  static const int pair_env = env_int("MOEINF_DEC1_PAIR", 1);  // 0: always the arrival-counter form; 4 / 8: waves per expert
-  if (s2.wdtype == DT_F8) {  // fp8 slots (gated families, bf16): the same two forms on fp8 tiles
-    if (s2.dtype != DT_BF16 || s2.comb.kind > 1 || (s2.K % 64) != 0) return hipErrorInvalidValue;
-    static const int pu = env_int("MOEINF_DEC1_PAIR_U", 4);
-    if (pair_env && s2.comb.K == 2 && !(s2.comb.kind == 1 && s2.comb.y_shared)) {
-      const dim3 g1((s2.R + 15) / 16);
-      if (pu == 8) KL((ffn2_decode1_pair_kernel<f8w_t, 4, 8>), g1, dim3(512), 0, st, s2);
-      else KL((ffn2_decode1_pair_kernel<f8w_t, 4, 4>), g1, dim3(512), 0, st, s2);
-      return hipGetLastError();
-    }
-    const dim3 grid((s2.R + 15) / 16, s2.comb.K);
-    static const int du = env_int("MOEINF_DEC1_U", 4);
-    if ((size_t)s2.K >= 16384) KL((ffn2_decode1_kernel<f8w_t, 8, 4>), grid, dim3(512), 0, st, s2);  // (as bf16: by weight bytes per row)
-    else if (du == 8) KL((ffn2_decode1_kernel<f8w_t, 4, 8>), grid, dim3(256), 0, st, s2);
-    else KL((ffn2_decode1_kernel<f8w_t, 4, 4>), grid, dim3(256), 0, st, s2);
-    return hipGetLastError();
-  }
-  if (s2.wdtype == DT_MX4) {  // MXFP4 slots (gated families, bf16): the same two forms on MXFP4 tiles
-    if (s2.dtype != DT_BF16 || s2.comb.kind > 1 || (s2.K % 128) != 0) return hipErrorInvalidValue;
-    static const int pu = env_int("MOEINF_DEC1_PAIR_U", 4);
-    if (pair_env && s2.comb.K == 2 && !(s2.comb.kind == 1 && s2.comb.y_shared)) {
-      const dim3 g1((s2.R + 15) / 16);
-      if (pu == 8) KL((ffn2_decode1_pair_kernel<mx4w_t, 4, 8>), g1, dim3(512), 0, st, s2);
-      else KL((ffn2_decode1_pair_kernel<mx4w_t, 4, 4>), g1, dim3(512), 0, st, s2);
-      return hipGetLastError();
-    }
-    const dim3 grid((s2.R + 15) / 16, s2.comb.K);
-    static const int du = env_int("MOEINF_DEC1_U", 4);
-    if ((size_t)s2.K >= 32768) KL((ffn2_decode1_kernel<mx4w_t, 8, 4>), grid, dim3(512), 0, st, s2);  // (as bf16: by weight bytes per row)
-    else if (du == 8) KL((ffn2_decode1_kernel<mx4w_t, 4, 8>), grid, dim3(256), 0, st, s2);
-    else KL((ffn2_decode1_kernel<mx4w_t, 4, 4>), grid, dim3(256), 0, st, s2);
-    return hipGetLastError();
-  }
-  if (pair_env && (s2.dtype == DT_BF16 || s2.dtype == DT_F16) && s2.comb.K == 2 && (s2.K % 32) == 0 && !(s2.comb.kind == 1 && s2.comb.y_shared) && s2.comb.kind <= 1) {
-    const dim3 g1((s2.R + 15) / 16);
-    // 4 waves per expert (8 per CU), batches of 4 tiles: 38.9 us per Mixtral launch; 8 waves per expert 40.5; the
-    // arrival-counter form 41.9
-    static const int pu = env_int("MOEINF_DEC1_PAIR_U", 4);
-    if (s2.dtype == DT_F16) KL((ffn2_decode1_pair_kernel<half_t, 4, 4>), g1, dim3(512), 0, st, s2);  // fp16: the default form only
-    else if (pair_env == 8) KL((ffn2_decode1_pair_kernel<uint16_t, 8, 4>), g1, dim3(1024), 0, st, s2);
-    else if (pu == 8) KL((ffn2_decode1_pair_kernel<uint16_t, 4, 8>), g1, dim3(512), 0, st, s2);
-    else if (pu == 2) KL((ffn2_decode1_pair_kernel<uint16_t, 4, 2>), g1, dim3(512), 0, st, s2);
-    else KL((ffn2_decode1_pair_kernel<uint16_t, 4, 4>), g1, dim3(512), 0, st, s2);
-    return hipGetLastError();
-  }
-  const dim3 grid((s2.R + 15) / 16, s2.comb.K);
-  if (s2.comb.kind == 2) {  // Switch, top-1: H/16 workgroups (48 for Switch-base) of sixteen waves
-    // twelve tiles per wave and batch: Switch-base's down projection is 192 tiles per row group = 16 waves x 12, i.e. the
-    // workgroup's whole 197 KB in flight at once (MOEINF_DEC1_SWITCH_U=4: three batches of four, 10.6 us per launch)
-    static const int su = env_int("MOEINF_DEC1_SWITCH_U", 12);
-    if (su == 12) {
-      if (s2.dtype == DT_BF16) KL((ffn2_decode1_kernel<uint16_t, 16, 12>), grid, dim3(1024), 0, st, s2);
-      else if (s2.dtype == DT_F16) KL((ffn2_decode1_kernel<half_t, 16, 12>), grid, dim3(1024), 0, st, s2);
-      else KL((ffn2_decode1_kernel<float, 16, 12>), grid, dim3(1024), 0, st, s2);
-      return hipGetLastError();
-    }
-    if (s2.dtype == DT_BF16) KL((ffn2_decode1_kernel<uint16_t, 16, 4>), grid, dim3(1024), 0, st, s2);
-    else if (s2.dtype == DT_F16) KL((ffn2_decode1_kernel<half_t, 16, 4>), grid, dim3(1024), 0, st, s2);
-    else KL((ffn2_decode1_kernel<float, 16, 4>), grid, dim3(1024), 0, st, s2);
-    return hipGetLastError();
-  }
-  if (s2.dtype == DT_F16) {  // fp16 gated families: the arrival-counter form
-    if ((size_t)s2.K * 2 >= 16384) KL((ffn2_decode1_kernel<half_t, 8, 4>), grid, dim3(512), 0, st, s2);
-    else KL((ffn2_decode1_kernel<half_t, 4, 4>), grid, dim3(256), 0, st, s2);
-    return hipGetLastError();
-  }
-  const size_t kbytes = (size_t)s2.K * 2;
-  static const int du = env_int("MOEINF_DEC1_U", 4);  // k-tiles per wave fetched per batch (short reductions)
-  if (kbytes >= 16384) KL((ffn2_decode1_kernel<uint16_t, 8, 4>), grid, dim3(512), 0, st, s2);
-  else if (du == 8) KL((ffn2_decode1_kernel<uint16_t, 4, 8>), grid, dim3(256), 0, st, s2);
-  else if (du == 12) KL((ffn2_decode1_kernel<uint16_t, 4, 12>), grid, dim3(256), 0, st, s2);
-  else KL((ffn2_decode1_kernel<uint16_t, 4, 4>), grid, dim3(256), 0, st, s2);
-  return hipGetLastError();
+// the form decode1_form chose (kernels.h) -> its instantiation
+hipError_t launch_ffn2_decode1(const FfnStage& s2, const Decode1Form& f, hipStream_t st) {
+  const bool slot = s2.wdtype == DT_F8 || s2.wdtype == DT_MX4;
+  if (slot && (s2.dtype != DT_BF16 || s2.comb.kind > 1 || (s2.K % (s2.wdtype == DT_MX4 ? 128 : 64)) != 0)) return hipErrorInvalidValue;
+  // the form must be this stage's: one workgroup (row) per 16 output rows and, in the arrival-counter form, per chosen expert; the pair
+  // kernel combines exactly two experts and no shared expert's row
+  if (f.grid_x != (s2.R + 15) / 16 || f.grid_y != (f.pair ? 1 : s2.comb.K) ||
+      (f.pair && (s2.comb.K != 2 || s2.comb.kind > 1 || (s2.comb.kind == 1 && s2.comb.y_shared)))) return hipErrorInvalidValue;
+  const dim3 grid(f.grid_x, f.grid_y);
+  const bool ok = with_kernel_type(s2.dtype, s2.wdtype, [&](auto t) {
+    using T = decltype(t);
+    constexpr bool SLOT = std::is_same<T, f8w_t>::value || std::is_same<T, mx4w_t>::value, B16 = std::is_same<T, uint16_t>::value, F32 = std::is_same<T, float>::value;
+    const auto is = [&](int pair, int waves, int unroll) { return f.pair == pair && f.waves == waves && f.unroll == unroll; };
+#define PAIR(NWE, UU) if (is(1, NWE, UU)) { KL((ffn2_decode1_pair_kernel<T, NWE, UU>), grid, dim3(2 * NWE * 64), 0, st, s2); return true; }
+#define CTR(NWV, UU) if (is(0, NWV, UU)) { KL((ffn2_decode1_kernel<T, NWV, UU>), grid, dim3(NWV * 64), 0, st, s2); return true; }
+    if constexpr (!F32) { PAIR(4, 4) CTR(8, 4) CTR(4, 4) }        // every 2-byte activation dtype and slot format
+    if constexpr (B16 || SLOT) { PAIR(4, 8) CTR(4, 8) }          // MOEINF_DEC1_PAIR_U / MOEINF_DEC1_U = 8
+    if constexpr (B16) { PAIR(4, 2) PAIR(8, 4) CTR(4, 12) }      // bf16's sweep forms
+    if constexpr (!SLOT) { CTR(16, 12) CTR(16, 4) }              // Switch, top-1
+#undef PAIR
+#undef CTR
+    return false;
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_route_index(const RouteArgs& r, const IndexArgs& a, hipStream_t st, const EpFuse* pack) {

@@ -206,35 +206,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void moe_
 }
 
 // bf16 / fp16 model with the gate in the model dtype or fp32; sh1 / sh2 = the hidden shared expert's stages or nullptr
-hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnStage* sh1, const FfnStage* sh2, const FfnStage& s1, const LayerSync& sy, hipStream_t st) {
+hipError_t launch_moe_front1(const RouteArgs& r, const IndexArgs& a, const FfnStage* sh1, const FfnStage* sh2, const FfnStage& s1, const LayerSync& sy, const SelfRouteForm& f, hipStream_t st) {
   const int n_rg = (s1.R + 15) / 16;
   const int n_sh1 = sh1 ? (sh1->R_sh + 15) / 16 : 0, n_sh2 = sh2 ? (sh2->R_sh + 15) / 16 : 0;
-  const dim3 grid(r.E + n_sh1 + 1 + r.K * n_rg + n_sh2);
-  // (as launch_ffn1_selfroute: a multi-round grid streams best with FOUR workgroups per CU, capped through dynamic LDS, and
-  // four tiles per wave, matrix and batch; a grid that is resident all at once takes eight)
-  static const int lds_env = env_int("MOEINF_SR_LDS_KB", -1);
-  const size_t dyn = (size_t)(lds_env >= 0 ? lds_env : (grid.x > 4 * 256 ? 30 : 0)) * 1024;
-  static const int sr_u_env = env_int("MOEINF_SR_U", 0);
-  const int sr_u = sr_u_env ? sr_u_env : (grid.x > 4 * 256 ? 4 : 8);
+  const bool slot = s1.wdtype == DT_F8 || s1.wdtype == DT_MX4;
+  if (slot && (s1.dtype != DT_BF16 || (s1.wdtype == DT_MX4 && (s1.K % 128) != 0))) return hipErrorInvalidValue;
+  if (f.grid != r.E + n_sh1 + 1 + r.K * n_rg + n_sh2 || (r.gate_dtype != s1.dtype && r.gate_dtype != DT_F32)) return hipErrorInvalidValue;
+  const dim3 grid(f.grid);
+  const size_t dyn = (size_t)f.lds_kb * 1024;
   const int rl = r.kind != 0 ? 0 : (r.x_dtype == DT_BF16 ? 1 : (r.x_dtype == DT_F16 ? 2 : 0));
   const FfnStage& a1 = sh1 ? *sh1 : s1;
   const FfnStage& a2 = sh2 ? *sh2 : s1;
-#define F1(TT, GW, UU) KL((moe_front1_kernel<TT, GW, UU>), grid, dim3(256), dyn, st, r, a, a1, a2, s1, sy, rl, n_sh1, n_sh2)
-#define F1U(TT, GW) do { if (sr_u == 8) F1(TT, GW, 8); else F1(TT, GW, 4); } while (0)
-  if (s1.wdtype == DT_F8) {  // fp8 slots (bf16)
-    if (s1.dtype != DT_BF16) return hipErrorInvalidValue;
-    if (r.gate_dtype == DT_BF16) F1U(f8w_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(f8w_t, float); else return hipErrorInvalidValue;
-  }
-  else if (s1.wdtype == DT_MX4) {  // MXFP4 slots (bf16)
-    if (s1.dtype != DT_BF16 || (s1.K % 128) != 0) return hipErrorInvalidValue;
-    if (r.gate_dtype == DT_BF16) F1U(mx4w_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(mx4w_t, float); else return hipErrorInvalidValue;
-  }
-  else if (s1.dtype == DT_BF16) { if (r.gate_dtype == DT_BF16) F1U(uint16_t, uint16_t); else if (r.gate_dtype == DT_F32) F1U(uint16_t, float); else return hipErrorInvalidValue; }
-  else if (s1.dtype == DT_F16) { if (r.gate_dtype == DT_F16) F1U(half_t, half_t); else if (r.gate_dtype == DT_F32) F1U(half_t, float); else return hipErrorInvalidValue; }
-  else return hipErrorInvalidValue;
-#undef F1U
+  const bool ok = with_kernel_type(s1.dtype, s1.wdtype, [&](auto t) {
+    using T = decltype(t);
+    using A = typename act_of<T>::type;
+    if constexpr (std::is_same<T, float>::value) return false;
+    else {
+#define F1(GW) do { if (f.tiles == 8) KL((moe_front1_kernel<T, GW, 8>), grid, dim3(256), dyn, st, r, a, a1, a2, s1, sy, rl, n_sh1, n_sh2); \
+                    else KL((moe_front1_kernel<T, GW, 4>), grid, dim3(256), dyn, st, r, a, a1, a2, s1, sy, rl, n_sh1, n_sh2); } while (0)
+      if (r.gate_dtype == DT_F32) F1(float); else F1(A);
 #undef F1
-  return hipGetLastError();
+      return true;
+    }
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -382,22 +377,14 @@ int layer1_switch_wgs_per_cu(int x_dtype, int gate_dtype) {
 }
 
 bool launch_moe_layer1_switch(const RouteArgs& r, const IndexArgs& a, const FfnStage& s1, const FfnStage& s2, const LayerSync& sy, int num_cus, int wgs_per_cu, hipStream_t st) {
-  if (s1.wdtype == DT_F8 || s2.wdtype == DT_F8 || s1.wdtype == DT_MX4 || s2.wdtype == DT_MX4) return false;  // (Switch experts never have fp8 or MXFP4 slots: moeinf_create_ex refuses them)
-  constexpr int KS = 4, P2 = 6, NW = 8;
-  const int n_rg = (s1.R + 15) / 16, n_col = (s2.R + 15) / 16;
-  const dim3 grid(r.E + 1 + n_rg + KS * n_col);
-  const int ept = s2.dtype == DT_F32 ? 16 : 32;
-  // every workgroup resident at once: what the chip HOLDS is asked (occupancy query), not assumed; at most two per CU even if more fit
-  const int per_cu = wgs_per_cu > 0 ? (wgs_per_cu < 2 ? wgs_per_cu : 2) : 0;
-  if (per_cu == 0 || (int)grid.x > per_cu * num_cus || (s2.K % (ept * KS)) != 0 || (s1.K % ept) != 0 || s2.K / ept / KS > NW * P2 || r.K != 1 || s2.dtype == DT_F16 || !sy.part) return false;
-  if (s2.dtype == DT_F32) {
-    if (r.gate_dtype != DT_F32) return false;
-    KL((moe_layer1_switch_kernel<float, float, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
-  } else {
-    if (r.gate_dtype == DT_BF16) KL((moe_layer1_switch_kernel<uint16_t, uint16_t, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
-    else if (r.gate_dtype == DT_F32) KL((moe_layer1_switch_kernel<uint16_t, float, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
-    else return false;
-  }
+  constexpr int KS = 4, P2 = 6;
+  // (Switch experts never have fp8 or MXFP4 slots: moeinf_create_ex refuses them)
+  if (s1.wdtype != s2.wdtype || !sy.part ||
+      !layer1_switch_fits(s2.dtype, r.gate_dtype, s1.wdtype, r.E, r.K, s1.R, s1.K, s2.R, s2.K, num_cus, wgs_per_cu)) return false;
+  const dim3 grid(r.E + 1 + (s1.R + 15) / 16 + KS * ((s2.R + 15) / 16));
+  if (s2.dtype == DT_F32) KL((moe_layer1_switch_kernel<float, float, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
+  else if (r.gate_dtype == DT_BF16) KL((moe_layer1_switch_kernel<uint16_t, uint16_t, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
+  else KL((moe_layer1_switch_kernel<uint16_t, float, P2, KS>), grid, dim3(512), 0, st, r, a, s1, s2, sy);
   return hipGetLastError() == hipSuccess;
 }
 
