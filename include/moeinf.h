@@ -186,6 +186,19 @@ int moeinf_ffn_f8_gemm_form(int nmat, int K, int K_sh, int R, int active, int ma
  * expert's stage in gate_shared1 / route_shared2; [22] stage 2 may fuse the combine; [23] its fuse mode; [24] stage 1 carries
  * its own kernel timer; [25] sleep repetitions between two counter polls of a fused launch (stage 1 = 4 or 5, else 0). */
 int moeinf_layer_form(const int32_t* shape, int n_shape, int32_t* out, int n_out);
+/* How the routed experts of an engine are held and moved: one pure function decides the weight format (csrc/transfer_plan.h
+ * weight_format) and one the transfer of an expert from its pinned host blob into its HBM slot (transfer_plan).
+ * Works without a GPU; reads the tier mover's environment knobs on every call.  shape[9]: dtype, gate_dtype (moeinf_config),
+ * slot_dtype (moeinf_create_options; -1: none given, moeinf_create), expert type, router kind, ep_size, hidden, inter, shared inter.
+ * Returns the refusal's error code (text in moeinf_last_error) with out[0] set to it, or MOEINF_OK and out[168]:
+ * [0] 0; [1..3] arithmetic / host blob / slot dtype (MOEINF_DTYPE_* or MOEINF_SLOT_MXFP4); [4] form: 0 pull kernel, 1 SDMA copy of
+ * the whole blob + one re-tile launch, 2 SDMA tensor by tensor; [5] one event serves both FFN stages; [6] fp8 -> bf16 up-cast on the
+ * way; [7] workgroups per pull launch; [8] stream the first write into the slot is ordered on (0 copy, 1 re-tile); [9] link-busy
+ * timing (0 the pull kernels' tick records, 1 an event pair); [10,11] bytes of a staging buffer, [12,13] bytes credited to h2d_bytes
+ * (low, high word); [14] steps; then per step s at 16 + 38 s: tensors, `ready1` is recorded behind it, and per tensor in copy order
+ * nine numbers: index in moeinf_expert_layout, offset in the host blob (low, high), offset in the slot (low, high), bytes in the
+ * host blob (low, high), R and K as the re-tile kernels take them (K = 0: a vector of R 16-byte pieces). */
+int moeinf_transfer_plan(const int32_t* shape, int n_shape, int32_t* out, int n_out);
 /* The fence ring (csrc/engine_internal.h): sync-free forwards record a fence event only every MOEINF_FENCE_EVERY-th time; a copy
  * that recycles a slot waits for the OLDEST recorded fence that covers the slot's last reader.  moeinf_fence_ring: entries in the
  * ring; moeinf_fence_cover_pos: the ring position that lookup returns (-1: no recorded fence covers `forward` yet) for

@@ -89,6 +89,7 @@ PROTOTYPES = {
     "moeinf_ffn_f8_gemm_form": (C.c_int, [C.c_int] * 7 + [_I32P]),
     "moeinf_ffn_form": (C.c_int, [C.c_int] * 9 + [_I32P]),
     "moeinf_layer_form": (C.c_int, [_I32P, C.c_int, _I32P, C.c_int]),
+    "moeinf_transfer_plan": (C.c_int, [_I32P, C.c_int, _I32P, C.c_int]),
     "moeinf_set_cache_policy": (C.c_int, [_P, C.c_int]),
     "moeinf_rows_estimate": (C.c_int, [C.c_int] * 3),
     "moeinf_fence_ring": (C.c_int, []),

@@ -114,6 +114,34 @@ extern "C" int moeinf_layer_form(const int32_t* shape, int n_shape, int32_t* out
   return MOEINF_OK;
 }
 
+// weight_format and transfer_plan (transfer_plan.h) for the 9 numbers of include/moeinf.h; the knobs as the environment holds them NOW
+extern "C" int moeinf_transfer_plan(const int32_t* shape, int n_shape, int32_t* out, int n_out) {
+  if (!shape || !out || n_shape != 9 || n_out != 168) return fail(MOEINF_ERR_INVALID, "moeinf_transfer_plan: 9 shape numbers in, 168 out");
+  const int expert_type = shape[3], H = shape[6], F = shape[7], Fs = shape[8];
+  if (H <= 0 || F <= 0 || Fs < 0) return fail(MOEINF_ERR_INVALID, "moeinf_transfer_plan: bad shape");
+  const MoverKnobs knobs = MoverKnobs::from_env();
+  const WeightFormat w = weight_format(shape[0], shape[1], shape[2], expert_type, shape[4], shape[5], H, F, knobs);
+  memset(out, 0, (size_t)n_out * sizeof(int32_t));
+  out[0] = w.err;
+  if (w.err != MOEINF_OK) return fail(w.err, "%s", w.why);
+  const BlobLayout lay = make_layout(expert_type, H, F, w.host_dt);
+  const BlobLayout lay_sh = Fs > 0 ? make_layout(expert_type, H, Fs, w.host_dt == DT_F8 ? DT_F8 : w.dt) : BlobLayout();
+  const TransferPlan p = transfer_plan(lay, make_dev_layout(expert_type, H, F, w.slot_dt), lay_sh, expert_type, w, knobs);
+  int32_t* o = out + 1;
+  auto put = [&o](int64_t v) { *o++ = (int32_t)(v & 0xffffffff); };
+  auto put64 = [&put](int64_t v) { put(v); put(v >> 32); };
+  for (int dt : {w.dt, w.host_dt, w.slot_dt}) put(dt == DT_MX4 ? MOEINF_SLOT_MXFP4 : dt);
+  put(p.form); put(p.one_event); put(p.src_f8); put(p.pull_wgs); put(p.write_on_copy ? 0 : 1); put(p.tick_timing ? 0 : 1);
+  put64(p.stage_bytes); put64(p.h2d_bytes); put(p.n_steps); put(0);
+  for (int k = 0; k < p.n_steps; ++k) {
+    const TransferStep& st = p.step[k];
+    o = out + 16 + 38 * k;
+    put(st.n); put(st.ready1_after);
+    for (int j = 0; j < st.n; ++j) { put(st.tensor[j]); put64(st.src_off[j]); put64(st.dst_off[j]); put64(st.bytes[j]); put(st.R[j]); put(st.K[j]); }
+  }
+  return MOEINF_OK;
+}
+
 extern "C" int moeinf_ffn_ring2_form(int dtype, int nmat, int K, int K_sh, int R, int active, int max_rows, int num_cus, int32_t* out5) {
   if (!out5 || (nmat != 1 && nmat != 2) || K <= 0 || R <= 0 || active <= 0) return fail(MOEINF_ERR_INVALID, "moeinf_ffn_ring2_form: bad arguments");
   const bool two_bytes = dtype == MOEINF_DTYPE_BF16 || dtype == MOEINF_DTYPE_F16;
@@ -147,20 +175,21 @@ static inline uint16_t f8e4m3_to_bf16_bits(uint8_t v) {
   return (uint16_t)(bits >> 16);
 }
 
-static int validate(const moeinf_config* c) {
+// dt / gate_dt: the arithmetic and gate dtypes weight_format derived from c->dtype / c->gate_dtype
+static int validate(const moeinf_config* c, int dt, int gate_dt) {
   if (!c) return fail(MOEINF_ERR_INVALID, "cfg is NULL");
   if (c->abi_version != MOEINF_ABI_VERSION) return fail(MOEINF_ERR_INVALID, "abi_version %d != %d", c->abi_version, MOEINF_ABI_VERSION);
   if (c->num_layers <= 0 || c->num_experts <= 0 || c->num_experts > 256) return fail(MOEINF_ERR_INVALID, "num_layers/num_experts out of range (experts <= 256)");
-  if (c->dtype != MOEINF_DTYPE_BF16 && c->dtype != MOEINF_DTYPE_F32 && c->dtype != MOEINF_DTYPE_F16) return fail(MOEINF_ERR_UNSUPPORTED, "dtype %d: bf16 (0), fp32 (1) and fp16 (2) are built (fp8, id 3, is not)", c->dtype);
-  if (c->gate_dtype != MOEINF_DTYPE_BF16 && c->gate_dtype != MOEINF_DTYPE_F32 && c->gate_dtype != MOEINF_DTYPE_F16) return fail(MOEINF_ERR_UNSUPPORTED, "gate_dtype %d", c->gate_dtype);
+  if (dt != MOEINF_DTYPE_BF16 && dt != MOEINF_DTYPE_F32 && dt != MOEINF_DTYPE_F16) return fail(MOEINF_ERR_UNSUPPORTED, "dtype %d: bf16 (0), fp32 (1) and fp16 (2) are built (fp8, id 3, is not)", dt);
+  if (gate_dt != MOEINF_DTYPE_BF16 && gate_dt != MOEINF_DTYPE_F32 && gate_dt != MOEINF_DTYPE_F16) return fail(MOEINF_ERR_UNSUPPORTED, "gate_dtype %d", gate_dt);
   // the gate is either in the model dtype or fp32 (DeepSeek); bf16 <-> fp16 mixes are not built
-  if (c->gate_dtype != MOEINF_DTYPE_F32 && c->dtype != MOEINF_DTYPE_F32 && c->gate_dtype != c->dtype) return fail(MOEINF_ERR_UNSUPPORTED, "gate_dtype %d with dtype %d", c->gate_dtype, c->dtype);
-  if (c->gate_dtype == MOEINF_DTYPE_F16 && c->dtype == MOEINF_DTYPE_F32) return fail(MOEINF_ERR_UNSUPPORTED, "an fp16 gate with fp32 activations is not built");
+  if (gate_dt != MOEINF_DTYPE_F32 && dt != MOEINF_DTYPE_F32 && gate_dt != dt) return fail(MOEINF_ERR_UNSUPPORTED, "gate_dtype %d with dtype %d", gate_dt, dt);
+  if (gate_dt == MOEINF_DTYPE_F16 && dt == MOEINF_DTYPE_F32) return fail(MOEINF_ERR_UNSUPPORTED, "an fp16 gate with fp32 activations is not built");
   switch (c->expert_type) {
     case MOEINF_EXPERT_SWITCH: case MOEINF_EXPERT_SWITCH_GATED: case MOEINF_EXPERT_NLLB: case MOEINF_EXPERT_FSGPT: case MOEINF_EXPERT_MIXTRAL: case MOEINF_EXPERT_DEEPSEEK: break;
     default: return fail(MOEINF_ERR_UNSUPPORTED, "expert_type %d is not one of the reference's (expert_module.h:13-18)", c->expert_type);
   }
-  const int ev = c->dtype == MOEINF_DTYPE_F32 ? 4 : 8;
+  const int ev = dt == MOEINF_DTYPE_F32 ? 4 : 8;
   if (c->hidden <= 0 || c->inter <= 0 || c->hidden % ev || c->inter % ev) return fail(MOEINF_ERR_INVALID, "hidden/inter must be positive multiples of %d", ev);
   if (c->shared_inter < 0 || c->shared_inter % ev) return fail(MOEINF_ERR_INVALID, "shared_inter must be a multiple of %d", ev);
   if (c->top_k <= 0 || c->top_k > 8 || c->top_k > c->num_experts) return fail(MOEINF_ERR_INVALID, "top_k must be in 1..min(8,E)");
@@ -202,8 +231,8 @@ static int alloc_token_workspace(moeinf_engine* g, int max_tokens) {
   CHK(dmalloc(&g->d_pair_slot, T * K)); CHK(dmalloc(&g->d_topk_w, T * K)); CHK(dmalloc(&g->d_router_prob, T));
   CHK(dmalloc(&g->d_slot_token, rows)); CHK(dmalloc(&g->d_slot_pair, rows));
   CHK(dmalloc(&g->d_chunk, ((T * K + 1023) / 1024 + 1) * (size_t)std::max(g->E, g->cfg.ep_size)));
-  HIPCHK(hipMalloc(&g->d_h, rows * (size_t)g->ldh * g->es));
-  HIPCHK(hipMalloc(&g->d_y, rows * (size_t)g->H * g->es));
+  HIPCHK(hipMalloc(&g->d_h, rows * (size_t)g->ldh * g->es()));
+  HIPCHK(hipMalloc(&g->d_y, rows * (size_t)g->H * g->es()));
   return MOEINF_OK;
 }
 
@@ -288,86 +317,34 @@ extern "C" int moeinf_destroy(moeinf_engine* g) {
 }
 
 static void prealloc_slots(moeinf_engine* g);
-enum SlotKind { SLOT_PLAIN = 0, SLOT_F8 = 1, SLOT_MX4 = 2 };  // what moeinf_create_ex asked the routed experts' slots to hold
-static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine** out);
-extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, SLOT_PLAIN, out); }
-
-// fp8 slots: what the fp8-weight kernels cover (kernels.hip / layer_fused.hip: the row-dot forms of the gated families); every
-// other configuration is refused here, so the kernels that have no fp8 form (ffn_form picks no such grouped GEMM; the
-// Switch one-launch layer, the expert-parallel owner kernels) are never reached
-static int check_fp8_slots(const moeinf_config* c) {
-  if (c->dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need fp8 experts (dtype %d, not %d)", MOEINF_DTYPE_F8E4M3, c->dtype);
-  if (c->expert_type != MOEINF_EXPERT_MIXTRAL && c->expert_type != MOEINF_EXPERT_DEEPSEEK)
-    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots are built for Mixtral and DeepSeek experts only (expert_type %d)", c->expert_type);
-  if (c->router_kind != MOEINF_ROUTER_MIXTRAL && c->router_kind != MOEINF_ROUTER_SOFTMAX_TOPK && c->router_kind != MOEINF_ROUTER_DEEPSEEK &&
-      c->router_kind != MOEINF_ROUTER_DEEPSEEK_V3)
-    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots: router_kind %d is not one of the Mixtral / DeepSeek families'", c->router_kind);
-  if (c->ep_size != 1) return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots are not built for expert parallelism (ep_size %d)", c->ep_size);
-  if (c->hidden <= 0 || c->inter <= 0 || c->hidden % 64 || c->inter % 64)
-    return fail(MOEINF_ERR_UNSUPPORTED, "fp8 slots need hidden and inter to be multiples of 64 (one fp8 tile: 64 k), not %d / %d", c->hidden, c->inter);
-  return MOEINF_OK;
-}
-// MXFP4 slots: a bf16 engine whose routed experts are OCP MXFP4 in the host tier, on the link and in their slots; decided here,
-// before any device call.  What the MXFP4-weight kernels cover is what the fp8-weight row-dot kernels cover, on 128-k tiles.
-static int check_mxfp4_slots(const moeinf_config* c) {
-  if (c->dtype != MOEINF_DTYPE_BF16) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots need a bf16 engine (dtype %d, not %d): the experts are up-cast to bf16 in registers", MOEINF_DTYPE_BF16, c->dtype);
-  if (c->gate_dtype != MOEINF_DTYPE_BF16 && c->gate_dtype != MOEINF_DTYPE_F32) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: gate_dtype %d is neither bf16 nor fp32", c->gate_dtype);
-  if (c->expert_type != MOEINF_EXPERT_MIXTRAL && c->expert_type != MOEINF_EXPERT_DEEPSEEK)
-    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are built for Mixtral and DeepSeek experts only (expert_type %d)", c->expert_type);
-  if (c->router_kind != MOEINF_ROUTER_MIXTRAL && c->router_kind != MOEINF_ROUTER_SOFTMAX_TOPK && c->router_kind != MOEINF_ROUTER_DEEPSEEK &&
-      c->router_kind != MOEINF_ROUTER_DEEPSEEK_V3)
-    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: router_kind %d is not one of the Mixtral / DeepSeek families'", c->router_kind);
-  if (c->ep_size != 1) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are not built for expert parallelism (ep_size %d)", c->ep_size);
-  if (c->hidden <= 0 || c->inter <= 0 || c->hidden % 128 || c->inter % 128)
-    return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots need hidden and inter to be multiples of 128 (one mxfp4 tile: 128 k), not %d / %d", c->hidden, c->inter);
-  // the tier mover re-orders the scales of whole row groups through 16 KiB of LDS (kernels.hip: mx4_scale_groups)
-  for (int K : {c->hidden, c->inter}) {
-    const int KB = K / 128, ga = (KB % 4 == 0) ? 1 : ((KB % 2 == 0) ? 2 : 4);
-    if (ga * KB * 64 > 16384) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots: a reduction length of %d is too long for the tier mover's scale units", K);
-  }
-  const char* pe = getenv("MOEINF_H2D_PULL");
-  if (pe && atoi(pe) == 0) return fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are filled by the PULL tier mover: not with MOEINF_H2D_PULL=0");
-  return MOEINF_OK;
-}
+// slot: moeinf_create_options.slot_dtype, -1 when the caller gave none
+static int create_engine(const moeinf_config* cfg, int slot, moeinf_engine** out);
+extern "C" int moeinf_create(const moeinf_config* cfg, moeinf_engine** out) { return create_engine(cfg, -1, out); }
 extern "C" int moeinf_create_ex(const moeinf_config* cfg, const moeinf_create_options* opts, moeinf_engine** out) {
   if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!cfg) return fail(MOEINF_ERR_INVALID, "cfg is NULL");
-  if (!opts) return create_engine(cfg, SLOT_PLAIN, out);
+  if (!opts) return create_engine(cfg, -1, out);
   if (opts->struct_bytes != (int32_t)sizeof(moeinf_create_options)) return fail(MOEINF_ERR_INVALID, "options.struct_bytes %d != %d", opts->struct_bytes, (int)sizeof(moeinf_create_options));
   for (int i = 0; i < 6; ++i) if (opts->reserved[i]) return fail(MOEINF_ERR_INVALID, "options.reserved[%d] must be zero", i);
-  if (opts->slot_dtype == MOEINF_SLOT_MXFP4) {
-    CHK(check_mxfp4_slots(cfg));
-    return create_engine(cfg, SLOT_MX4, out);
-  }
-  // (fp8 experts: slot_dtype bf16 = today's engine, the pull kernel up-casts into bf16 slots)
-  const bool plain = opts->slot_dtype == cfg->dtype || (cfg->dtype == MOEINF_DTYPE_F8E4M3 && opts->slot_dtype == MOEINF_DTYPE_BF16);
-  if (plain && opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return create_engine(cfg, SLOT_PLAIN, out);
-  if (opts->slot_dtype != MOEINF_DTYPE_F8E4M3) return fail(MOEINF_ERR_UNSUPPORTED, "slot_dtype %d with dtype %d: only fp8 slots (%d) for fp8 experts are built", opts->slot_dtype, cfg->dtype, MOEINF_DTYPE_F8E4M3);
-  CHK(check_fp8_slots(cfg));
-  return create_engine(cfg, SLOT_F8, out);
+  if (opts->slot_dtype < 0) return fail(MOEINF_ERR_UNSUPPORTED, "slot_dtype %d", opts->slot_dtype);
+  return create_engine(cfg, opts->slot_dtype, out);
 }
 extern "C" int moeinf_slot_dtype(const moeinf_engine* g, int32_t* slot_dtype) {
   if (!g || !slot_dtype) return fail(MOEINF_ERR_INVALID, "engine or slot_dtype is NULL");
-  *slot_dtype = g->slot_mx4 ? MOEINF_SLOT_MXFP4 : (g->slot_f8 ? MOEINF_DTYPE_F8E4M3 : g->cfg.dtype);
+  *slot_dtype = g->slot_dt == DT_MX4 ? MOEINF_SLOT_MXFP4 : g->slot_dt;  // (DT_BF16 .. DT_F8 are the C ABI's ids)
   return MOEINF_OK;
 }
 
-static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine** out) {
-  const bool slot_f8 = slot == SLOT_F8, slot_mx4 = slot == SLOT_MX4;
+static int create_engine(const moeinf_config* cfg, int slot, moeinf_engine** out) {
   if (!out) return fail(MOEINF_ERR_INVALID, "out is NULL");
   *out = nullptr;
-  // fp8 experts (the reference's dtype id 3, core/parallel/expert_module.h:23,118-119): e4m3fn bytes in the HOST tier and on the link,
-  // up-cast to bf16 when an expert is pulled into its HBM slot; activations, gate and all arithmetic are bf16 — y = FFN(x; W.to(bf16)),
-  // what torch::linear over up-cast weights computes.  Everything behind the tier mover sees a bf16 engine.
-  moeinf_config cfg_local;
-  bool host_f8 = false;
-  if (cfg && cfg->dtype == MOEINF_DTYPE_F8E4M3) {
-    cfg_local = *cfg; cfg_local.dtype = MOEINF_DTYPE_BF16; host_f8 = true;
-    if (cfg_local.gate_dtype == MOEINF_DTYPE_F8E4M3) cfg_local.gate_dtype = MOEINF_DTYPE_BF16;
-    cfg = &cfg_local;
-  }
-  CHK(validate(cfg));
+  if (!cfg) return fail(MOEINF_ERR_INVALID, "cfg is NULL");
+  // what is refused about the weight format is refused here, before any device call (transfer_plan.h)
+  const MoverKnobs knobs = MoverKnobs::from_env();
+  const WeightFormat wf = weight_format(cfg->dtype, cfg->gate_dtype, slot, cfg->expert_type, cfg->router_kind, cfg->ep_size, cfg->hidden, cfg->inter, knobs);
+  if (wf.err != MOEINF_OK) return fail(wf.err, "%s", wf.why);
+  CHK(validate(cfg, wf.dt, wf.gate_dt));
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(MOEINF_ERR_INVALID, "device_id %d but %d HIP devices visible", cfg->device_id, ndev);
@@ -388,18 +365,15 @@ static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine*
   for (int i = 0; i < kFenceRing; ++i) g->fence_ev[i] = nullptr;
   g->L = cfg->num_layers; g->E = cfg->num_experts; g->K = cfg->top_k; g->H = cfg->hidden; g->F = cfg->inter; g->Fs = cfg->shared_inter;
   g->has_shared = cfg->shared_inter > 0;
-  g->dt = cfg->dtype == MOEINF_DTYPE_BF16 ? DT_BF16 : (cfg->dtype == MOEINF_DTYPE_F16 ? DT_F16 : DT_F32);
-  g->es = dt_bytes(g->dt);
-  g->host_f8 = host_f8;
-  g->host_es = host_f8 ? 1 : g->es;
-  g->slot_mx4 = slot_mx4;  // (never with fp8 experts: check_mxfp4_slots refused them)
-  g->lay = make_layout(cfg->expert_type, g->H, g->F, g->host_es, g->slot_mx4);
-  if (g->has_shared) g->lay_sh = make_layout(cfg->expert_type, g->H, g->Fs, g->host_es);
-  // fp8 slots: the routed experts' tiles hold e4m3fn bytes (pull_retile_kernel<uint8_t, false>); the shared expert stays bf16
-  g->slot_f8 = slot_f8 && host_f8;
-  g->slot_dt = g->slot_f8 ? DT_F8 : (g->slot_mx4 ? DT_MX4 : g->dt);  // (MXFP4 slots: the shared expert stays bf16, too)
-  g->dlay = make_dev_layout(cfg->expert_type, g->H, g->F, g->slot_dt, g->slot_f8 ? 1 : g->es);
-  if (g->has_shared) g->dlay_sh = make_dev_layout(cfg->expert_type, g->H, g->Fs, g->dt, g->es);
+  g->dt = wf.dt; g->host_dt = wf.host_dt; g->slot_dt = wf.slot_dt; g->gate_dt = wf.gate_dt;
+  g->knobs = knobs;
+  g->lay = make_layout(cfg->expert_type, g->H, g->F, g->host_dt);
+  g->dlay = make_dev_layout(cfg->expert_type, g->H, g->F, g->slot_dt);
+  if (g->has_shared) {  // the shared expert is always resident, in `dt`: fp8 blobs are up-cast on the host, MXFP4 engines keep it bf16
+    g->lay_sh = make_layout(cfg->expert_type, g->H, g->Fs, g->host_dt == DT_F8 ? DT_F8 : g->dt);
+    g->dlay_sh = make_dev_layout(cfg->expert_type, g->H, g->Fs, g->dt);
+  }
+  g->plan = transfer_plan(g->lay, g->dlay, g->lay_sh, cfg->expert_type, wf, knobs);
   g->slot_bytes = g->dlay.total;
   g->nodes.resize((size_t)g->L * g->E);
   g->pol.resize((size_t)g->L * g->E);
@@ -429,7 +403,6 @@ static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine*
   TRYHIP(hipStreamCreateWithPriority(&g->demand.retile, hipStreamNonBlocking, hi));
   TRYHIP(hipStreamCreateWithPriority(&g->prefetch.copy, hipStreamNonBlocking, lo));
   TRYHIP(hipStreamCreateWithPriority(&g->prefetch.retile, hipStreamNonBlocking, lo));
-  if (const char* w = getenv("MOEINF_PREFETCH_WINDOW")) g->prefetch_window = std::max(1, atoi(w));
   TRYHIP(hipEventCreateWithFlags(&g->route_ev, hipEventDisableTiming));
   for (int i = 0; i < kFenceRing; ++i) TRYHIP(hipEventCreateWithFlags(&g->fence_ev[i], hipEventDisableTiming));
 
@@ -458,46 +431,17 @@ static int create_engine(const moeinf_config* cfg, SlotKind slot, moeinf_engine*
   TRYHIP(hipMemset(g->d_n_active, 0, sizeof(int32_t)));
   TRY(alloc_token_workspace(g, cfg->max_tokens));
   if (g->has_shared) {
-    TRYHIP(hipMalloc(&g->d_h_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->Fs * g->es));
-    TRYHIP(hipMalloc(&g->d_y_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->H * g->es));
+    TRYHIP(hipMalloc(&g->d_h_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->Fs * g->es()));
+    TRYHIP(hipMalloc(&g->d_y_sh, (size_t)HIDE_SHARED_MAX_TOKENS * g->H * g->es()));
   }
-  for (int i = 0; i < 4; ++i) g->stage_bytes = std::max<int64_t>(g->stage_bytes, std::max(align_up(g->lay.size[i], kAioAlignment), align_up(g->lay_sh.size[i] * (g->host_f8 ? 2 : 1), kAioAlignment)));
-  {
-    // whole-blob transfers for experts up to MOEINF_H2D_WHOLE_BLOB_MB (64; 0 = always tensor by tensor): DeepSeek-V2-Lite's
-    // 16.5 MiB expert was three 5.5 MiB copies with an event pair and a re-tile launch each: 46 GB/s against the 54.5 that
-    // Mixtral's 112 MiB pieces reach (round 5 offload leg)
-    const char* e = getenv("MOEINF_H2D_WHOLE_BLOB_MB");
-    const int64_t cap = (e ? atoll(e) : 64) << 20;
-    bool vec_ok = true;
-    for (int i = 0; i < g->dlay.n; ++i) if (g->dlay.K[i] == 0 && (g->dlay.size[i] % 16) != 0) vec_ok = false;
-    g->whole_blob = g->lay.total <= cap && vec_ok;
-    // MOEINF_H2D_PULL (default 1): the pull form needs 16-byte vector pieces like the whole-blob re-tile; MOEINF_H2D_PULL_WGS: workgroups per launch
-    const char* pe = getenv("MOEINF_H2D_PULL");
-    g->h2d_pull = (pe ? atoi(pe) != 0 : true) && vec_ok;
-    const char* pw = getenv("MOEINF_H2D_PULL_WGS");
-    // 16 workgroups with four 16-byte loads per lane in flight pull at the link's rate, fp8 blobs included (8: -3 %, 32: -2...6 %;
-    // profiles/r06_tier_mover_pull_vs_sdma_ab.txt)
-    g->h2d_pull_wgs = pw ? std::max(1, atoi(pw)) : 16;
-    // MOEINF_FENCE_EVERY (default 16; 1 = a fence behind every forward): how often a sync-free forward records its fence
-    const char* fe = getenv("MOEINF_FENCE_EVERY");
-    g->fence_every = fe ? std::min(std::max(1, atoi(fe)), kMirrorPool / 4) : 16;
-    if (g->host_f8) {  // the fp8 pull loads 16 source bytes (sixteen elements) per lane
-      bool ok16 = true;
-      for (int i = 0; i < g->dlay.n; ++i) ok16 = ok16 && (g->dlay.K[i] > 0 ? g->dlay.K[i] % 16 == 0 : g->dlay.size[i] % 32 == 0);
-      if (!ok16) { fail(MOEINF_ERR_UNSUPPORTED, "fp8 experts (dtype 3): hidden / inter (and bias lengths) must be multiples of 16"); return bail(MOEINF_ERR_UNSUPPORTED); }
-    }
-    if (g->slot_mx4 && !g->h2d_pull) { fail(MOEINF_ERR_UNSUPPORTED, "mxfp4 slots are filled by the PULL tier mover: not with MOEINF_H2D_PULL=0"); return bail(MOEINF_ERR_UNSUPPORTED); }
-    if (g->host_f8 && !g->h2d_pull) { fail(MOEINF_ERR_UNSUPPORTED, "fp8 experts (dtype 3) are up-cast by the PULL tier mover: not with MOEINF_H2D_PULL=0, nor with bias vectors that are not 16-byte multiples"); return bail(MOEINF_ERR_UNSUPPORTED); }
-    if (g->h2d_pull) {
-      TRYHIP(hipMalloc((void**)&g->d_copy_ts, (size_t)kCopyTsRing * 32));
-      TRYHIP(hipMemset(g->d_copy_ts, 0, (size_t)kCopyTsRing * 32));
-      g->copy_ts_expect.assign(kCopyTsRing, 0);
-    }
-    if (g->whole_blob) g->stage_bytes = std::max<int64_t>(g->stage_bytes, align_up(g->lay.total, kAioAlignment));
+  if (g->plan.tick_timing) {
+    TRYHIP(hipMalloc((void**)&g->d_copy_ts, (size_t)kCopyTsRing * 32));
+    TRYHIP(hipMemset(g->d_copy_ts, 0, (size_t)kCopyTsRing * 32));
+    g->copy_ts_expect.assign(kCopyTsRing, 0);
   }
   for (CopyLane* ln : {&g->demand, &g->prefetch}) {
     for (auto& b : ln->ring) {
-      TRYHIP(hipMalloc(&b.dev, (size_t)g->stage_bytes));
+      TRYHIP(hipMalloc(&b.dev, (size_t)g->plan.stage_bytes));
       TRYHIP(hipEventCreateWithFlags(&b.filled, hipEventDisableTiming));
       TRYHIP(hipEventCreateWithFlags(&b.freed, hipEventDisableTiming));
     }
@@ -591,7 +535,7 @@ extern "C" int moeinf_register_shared(moeinf_engine* g, int layer, const void* b
   for (int i = 0; i < g->dlay_sh.n; ++i) {
     const void* src = (const char*)blob + g->lay_sh.off[i];
     size_t bytes = (size_t)g->lay_sh.size[i];
-    if (g->host_f8) {
+    if (g->host_dt == DT_F8) {
       up.resize(bytes);
       for (size_t j = 0; j < bytes; ++j) up[j] = f8e4m3_to_bf16_bits(((const uint8_t*)src)[j]);
       src = up.data(); bytes *= 2;
@@ -633,8 +577,7 @@ static void drop_ready_count(moeinf_engine* g, int idx) {
 // one: a hipMalloc of a 336 MiB slot costs milliseconds and would sit on the demand-miss path.  If physical memory runs
 // out before the budget does, the cache simply has fewer slots.  MOEINF_PREALLOC=0 restores first-touch allocation.
 static void prealloc_slots(moeinf_engine* g) {
-  static const bool on = getenv("MOEINF_PREALLOC") ? atoi(getenv("MOEINF_PREALLOC")) != 0 : true;
-  if (!on) return;
+  if (!g->knobs.prealloc) return;
   while ((int64_t)g->slots.size() < g->max_slots && !g->slab_exhausted) {
     void* p = nullptr;
     if (hipMalloc(&p, (size_t)g->slot_bytes) != hipSuccess) {
@@ -716,19 +659,90 @@ static int retile_tensor(const moeinf_engine* g, const DevLayout& dl, int i, con
   return MOEINF_OK;
 }
 
-// Copy order of a blob's tensors: what FFN stage 1 reads first (w1 AND w3 / gate AND up / fc1 + bias / wi), then
-// the stage-2 tensors — so the compute stream can start stage 1 while the down projection is still on the link.
-// Returns the number of stage-1 tensors.
-static int copy_order(int expert_type, int order[4]) {
-  switch (expert_type) {
-    case MOEINF_EXPERT_MIXTRAL: order[0] = 0; order[1] = 2; order[2] = 1; return 2;   // w1 w3 | w2
-    case MOEINF_EXPERT_DEEPSEEK: case MOEINF_EXPERT_SWITCH_GATED: order[0] = 0; order[1] = 1; order[2] = 2; return 2;  // gate up | down
-    case MOEINF_EXPERT_NLLB: case MOEINF_EXPERT_FSGPT: order[0] = 0; order[1] = 1; order[2] = 2; order[3] = 3; return 2;  // fc1.w fc1.b | fc2.w fc2.b
-    default: order[0] = 0; order[1] = 1; return 1;                                     // wi | wo
-  }
-}
-
 static int ensure_host(moeinf_engine* g, int idx);
+
+// ---- the tier mover: issue_copy executes the engine's TransferPlan (transfer_plan.h), one executor per form ----
+// First write into slot s on stream ws.  (a) kernels of forward #last_use_seq may still read the previous tenant: wait for a fence
+// that covers it (fence_for records one if the sync-free forwards since have not); (b) the previous tenant's OWN transfer may still
+// be in flight on another lane (a prefetched expert is evictable from the moment its copy is issued): write-after-write on the slot
+static int order_first_write(moeinf_engine* g, const Slot& s, int victim, hipStream_t ws) {
+  if (s.last_use_seq > 0) {
+    hipEvent_t fe = nullptr;
+    CHK(fence_for(g, std::min(s.last_use_seq, g->seq), &fe));
+    if (hipEventQuery(fe) != hipSuccess) {
+      (void)hipGetLastError();
+      HIPCHK(hipStreamWaitEvent(ws, fe, 0));
+    }
+  }
+  if (victim >= 0) {
+    Node& vn = g->nodes[victim];
+    if (!vn.ready_waited && vn.ready && hipEventQuery(vn.ready) != hipSuccess) {
+      (void)hipGetLastError();
+      HIPCHK(hipStreamWaitEvent(ws, vn.ready, 0));
+    }
+    vn.ready_waited = true; vn.waited1 = true;
+  }
+  return MOEINF_OK;
+}
+// the tensors of one step, from blob `src` into slot `dst`
+static RetileBlob step_blob(const TransferStep& st, const void* src, void* dst, bool src_f8) {
+  RetileBlob rb;
+  memset(&rb, 0, sizeof rb);
+  rb.src = src; rb.dst = dst; rb.n = st.n; rb.src_f8 = src_f8 ? 1 : 0;
+  for (int j = 0; j < st.n; ++j) { rb.src_off[j] = st.src_off[j]; rb.dst_off[j] = st.dst_off[j]; rb.R[j] = st.R[j]; rb.K[j] = st.K[j]; }
+  return rb;
+}
+// PULL: one launch per step on the copy stream; the launches of one expert share a timing record
+static int run_pull(moeinf_engine* g, const Node& n, const Slot& s, CopyLane& ln, int victim) {
+  const TransferPlan& p = g->plan;
+  CHK(order_first_write(g, s, victim, ln.copy));
+  if (g->copy_ts_head - g->copy_ts_tail >= (uint64_t)kCopyTsRing) g->copy_ts_tail = g->copy_ts_head - kCopyTsRing + 1;  // overflow: the oldest records are given up
+  const int ts_slot = (int)(g->copy_ts_head % kCopyTsRing);
+  for (int k = 0; k < p.n_steps; ++k) {
+    HIPCHK(launch_pull_retile(step_blob(p.step[k], n.host, s.dev, p.src_f8), g->slot_dt, p.pull_wgs, ln.copy, g->d_copy_ts + (size_t)ts_slot * 4, k == 0 ? 1 : 0));
+    if (p.step[k].ready1_after) HIPCHK(hipEventRecord(n.ready1, ln.copy));
+  }
+  g->copy_ts_expect[ts_slot] += (uint64_t)p.n_steps * (uint64_t)p.pull_wgs;
+  g->copy_ts_head += 1;
+  return MOEINF_OK;
+}
+// the lane's next staging buffer, filled with `bytes` from the host on the copy stream; the re-tile stream is ordered behind the fill
+static int stage_in(CopyLane& ln, const void* src, int64_t bytes, StageBuf** out) {
+  StageBuf& b = ln.ring[ln.next];
+  ln.next = (ln.next + 1) % kStageRing;
+  if (b.used) HIPCHK(hipStreamWaitEvent(ln.copy, b.freed, 0));  // its previous content has been re-tiled
+  HIPCHK(hipMemcpyAsync(b.dev, src, (size_t)bytes, hipMemcpyHostToDevice, ln.copy));
+  HIPCHK(hipEventRecord(b.filled, ln.copy));
+  HIPCHK(hipStreamWaitEvent(ln.retile, b.filled, 0));
+  *out = &b;
+  return MOEINF_OK;
+}
+static int stage_out(CopyLane& ln, StageBuf& b) {
+  HIPCHK(hipEventRecord(b.freed, ln.retile));
+  b.used = true;
+  return MOEINF_OK;
+}
+// SDMA_BLOB: the whole blob with one copy, re-tiled by one launch
+static int run_sdma_blob(moeinf_engine* g, const Node& n, const Slot& s, CopyLane& ln, int victim) {
+  StageBuf* b = nullptr;
+  CHK(stage_in(ln, n.host, g->lay.total, &b));
+  CHK(order_first_write(g, s, victim, ln.retile));
+  HIPCHK(launch_retile_blob(step_blob(g->plan.step[0], b->dev, s.dev, false), g->dt, ln.retile));
+  return stage_out(ln, *b);
+}
+// SDMA_TENSORS: tensor i+1 is copied into the next staging buffer while tensor i is re-tiled into the slot
+static int run_sdma_tensors(moeinf_engine* g, const Node& n, const Slot& s, CopyLane& ln, int victim) {
+  for (int k = 0; k < g->plan.n_steps; ++k) {
+    const TransferStep& st = g->plan.step[k];
+    StageBuf* b = nullptr;
+    CHK(stage_in(ln, (const char*)n.host + st.src_off[0], st.bytes[0], &b));
+    if (k == 0) CHK(order_first_write(g, s, victim, ln.retile));
+    CHK(retile_tensor(g, g->dlay, st.tensor[0], b->dev, s.dev, ln.retile));
+    CHK(stage_out(ln, *b));
+    if (st.ready1_after) HIPCHK(hipEventRecord(n.ready1, ln.retile));
+  }
+  return MOEINF_OK;
+}
 
 // start the H2D transfer of node idx into a slot on lane `ln` (reference: Node::SetDevice host->device leg,
 // model_topology.cpp:102-119, which is a cudaMemcpyAsync + cudaStreamSynchronize of the whole blob)
@@ -741,131 +755,18 @@ static int issue_copy(moeinf_engine* g, int idx, CopyLane& ln, bool allow_protec
   Slot& s = g->slots[slot];
   if (!n.ready) HIPCHK(hipEventCreateWithFlags(&n.ready, hipEventDisableTiming));
   if (!n.ready1) HIPCHK(hipEventCreateWithFlags(&n.ready1, hipEventDisableTiming));
-  // link-busy timers: the pull form times itself inside its kernels (no queue packets); the SDMA forms bracket the copies with events
-  hipEvent_t start = g->h2d_pull ? nullptr : get_event(g), stop = g->h2d_pull ? nullptr : get_event(g);
+  const TransferPlan& p = g->plan;
+  // link-busy interval of the SDMA forms: first to last hipMemcpyAsync of this expert
+  hipEvent_t start = p.tick_timing ? nullptr : get_event(g), stop = p.tick_timing ? nullptr : get_event(g);
   if (start && stop) HIPCHK(hipEventRecord(start, ln.copy));
-  int order[4];
-  const int n1 = copy_order(g->cfg.expert_type, order);
-  // first write into the slot.  (a) kernels of forward #last_use_seq may still read the previous tenant: wait for a fence
-  // that covers it (fence_for records one if the sync-free forwards since have not);
-  // (b) the previous tenant's OWN transfer may still be in flight on another lane (a prefetched expert is
-  // evictable from the moment its copy is issued): write-after-write on the slot
-  auto order_first_write_on = [&](hipStream_t ws) -> int {
-    if (s.last_use_seq > 0) {
-      hipEvent_t fe = nullptr;
-      CHK(fence_for(g, std::min(s.last_use_seq, g->seq), &fe));
-      if (hipEventQuery(fe) != hipSuccess) {
-        (void)hipGetLastError();
-        HIPCHK(hipStreamWaitEvent(ws, fe, 0));
-      }
-    }
-    if (victim >= 0) {
-      Node& vn = g->nodes[victim];
-      if (!vn.ready_waited && vn.ready && hipEventQuery(vn.ready) != hipSuccess) {
-        (void)hipGetLastError();
-        HIPCHK(hipStreamWaitEvent(ws, vn.ready, 0));
-      }
-      vn.ready_waited = true; vn.waited1 = true;
-    }
-    return MOEINF_OK;
-  };
-  auto order_first_write = [&]() -> int { return order_first_write_on(ln.retile); };
-  if (g->h2d_pull) {
-    // PULL (kernels.hip: pull_retile_kernel): the copy stream's own kernel reads the pinned host blob and writes the tiled slot.
-    // Small experts: one launch for the whole blob; big ones: the stage-1 tensors first (ready1), then the rest.
-    CHK(order_first_write_on(ln.copy));
-    unsigned long long* ts = nullptr;
-    int ts_slot = -1;
-    if (g->d_copy_ts) {
-      if (g->copy_ts_head - g->copy_ts_tail >= (uint64_t)kCopyTsRing) g->copy_ts_tail = g->copy_ts_head - kCopyTsRing + 1;  // overflow: the oldest records are given up
-      ts_slot = (int)(g->copy_ts_head % kCopyTsRing);
-      ts = g->d_copy_ts + (size_t)ts_slot * 4;
-    }
-    int launches = 0;
-    auto pull = [&](int k0, int k1) -> int {
-      RetileBlob rb;
-      memset(&rb, 0, sizeof rb);
-      rb.src = n.host; rb.dst = s.dev; rb.n = 0; rb.src_f8 = (g->host_f8 && !g->slot_f8) ? 1 : 0;  // (fp8 slots: bytes as they are)
-      for (int k = k0; k < k1; ++k) {
-        const int i = order[k], j = rb.n++;
-        rb.src_off[j] = g->lay.off[i]; rb.dst_off[j] = g->dlay.off[i];
-        rb.K[j] = g->dlay.K[i];
-        rb.R[j] = g->dlay.K[i] > 0 ? g->dlay.R[i] : (int)(g->dlay.size[i] / 16);
-      }
-      HIPCHK(launch_pull_retile(rb, g->slot_dt, g->h2d_pull_wgs, ln.copy, ts, launches == 0 ? 1 : 0));
-      launches += 1;
-      return MOEINF_OK;
-    };
-    bool one_event = false;
-    if (g->whole_blob || n1 >= g->lay.n) {
-      CHK(pull(0, g->lay.n));
-      one_event = true;  // stage 1 and stage 2 wait for the same point of the stream: ONE event record serves both
-    } else {
-      CHK(pull(0, n1));
-      HIPCHK(hipEventRecord(n.ready1, ln.copy));
-      CHK(pull(n1, g->lay.n));
-    }
-    if (ts_slot >= 0) {
-      g->copy_ts_expect[ts_slot] += (uint64_t)launches * (uint64_t)g->h2d_pull_wgs;
-      g->copy_ts_head += 1;
-    }
-    HIPCHK(hipEventRecord(n.ready, ln.copy));
-    n.ready1_is_ready = one_event;
-    n.slot = slot;
-    n.ready_waited = false;
-    n.waited1 = false;
-    n.copy_inflight = true;
-    n.copy_seq = ++g->copy_seq; n.copy_lane = (&ln == &g->prefetch) ? 1 : 0;
-    n.host_clock = ++g->host_clock;
-    s.node = idx;
-    g->pol[idx].resident = true;
-    g->st.slots_used += 1;
-    g->st.h2d_bytes += g->lay.total;
-    queue_poke(g, idx % g->L, idx / g->L, (uint64_t)s.dev);
-    return MOEINF_OK;
-  }
-  bool sdma_one_event = false;
-  if (g->whole_blob) {
-    StageBuf& b = ln.ring[ln.next];
-    ln.next = (ln.next + 1) % kStageRing;
-    if (b.used) HIPCHK(hipStreamWaitEvent(ln.copy, b.freed, 0));  // its previous content has been re-tiled
-    HIPCHK(hipMemcpyAsync(b.dev, n.host, (size_t)g->lay.total, hipMemcpyHostToDevice, ln.copy));
-    HIPCHK(hipEventRecord(b.filled, ln.copy));
-    HIPCHK(hipStreamWaitEvent(ln.retile, b.filled, 0));
-    CHK(order_first_write());
-    RetileBlob rb;
-    memset(&rb, 0, sizeof rb);
-    rb.src = b.dev; rb.dst = s.dev; rb.n = g->lay.n;
-    for (int i = 0; i < g->lay.n; ++i) {
-      rb.src_off[i] = g->lay.off[i]; rb.dst_off[i] = g->dlay.off[i];
-      rb.K[i] = g->dlay.K[i];
-      rb.R[i] = g->dlay.K[i] > 0 ? g->dlay.R[i] : (int)(g->dlay.size[i] / 16);
-    }
-    HIPCHK(launch_retile_blob(rb, g->dt, ln.retile));
-    HIPCHK(hipEventRecord(b.freed, ln.retile));
-    b.used = true;
-    sdma_one_event = true;  // (`ready`, recorded below at the same point of the re-tile stream, serves for both)
-  } else
-  for (int k = 0; k < g->lay.n; ++k) {
-    const int i = order[k];
-    StageBuf& b = ln.ring[ln.next];
-    ln.next = (ln.next + 1) % kStageRing;
-    if (b.used) HIPCHK(hipStreamWaitEvent(ln.copy, b.freed, 0));  // its previous content has been re-tiled
-    HIPCHK(hipMemcpyAsync(b.dev, (const char*)n.host + g->lay.off[i], (size_t)g->lay.size[i], hipMemcpyHostToDevice, ln.copy));
-    HIPCHK(hipEventRecord(b.filled, ln.copy));
-    HIPCHK(hipStreamWaitEvent(ln.retile, b.filled, 0));
-    if (k == 0) CHK(order_first_write());
-    CHK(retile_tensor(g, g->dlay, i, b.dev, s.dev, ln.retile));
-    HIPCHK(hipEventRecord(b.freed, ln.retile));
-    b.used = true;
-    if (k == n1 - 1) HIPCHK(hipEventRecord(n.ready1, ln.retile));
-  }
+  CHK(p.form == MOVE_PULL ? run_pull(g, n, s, ln, victim)
+      : p.form == MOVE_SDMA_BLOB ? run_sdma_blob(g, n, s, ln, victim) : run_sdma_tensors(g, n, s, ln, victim));
   if (start && stop) {
-    HIPCHK(hipEventRecord(stop, ln.copy));  // link-busy interval: first to last hipMemcpyAsync of this expert
+    HIPCHK(hipEventRecord(stop, ln.copy));
     g->copy_timers.push_back({start, stop});
   }
-  HIPCHK(hipEventRecord(n.ready, ln.retile));
-  n.ready1_is_ready = sdma_one_event;
+  HIPCHK(hipEventRecord(n.ready, p.write_on_copy ? ln.copy : ln.retile));
+  n.ready1_is_ready = p.one_event;
   n.slot = slot;
   n.ready_waited = false;
   n.waited1 = false;
@@ -875,7 +776,7 @@ static int issue_copy(moeinf_engine* g, int idx, CopyLane& ln, bool allow_protec
   s.node = idx;
   g->pol[idx].resident = true;
   g->st.slots_used += 1;
-  g->st.h2d_bytes += g->lay.total;
+  g->st.h2d_bytes += p.h2d_bytes;
   queue_poke(g, idx % g->L, idx / g->L, (uint64_t)s.dev);
   return MOEINF_OK;
 }
@@ -956,10 +857,7 @@ static void settle_copy_timers(moeinf_engine* g, bool wait) {
 // needed host blob that can be re-read from disk gives up its arena block (reference: Node::SetDevice(DISK),
 // model_topology.cpp:76-88) and the wanted expert is read disk -> pinned host (-> HBM by the caller).
 static PrioAioPool* aio_pool(moeinf_engine* g) {
-  if (!g->aio) {
-    const char* t = getenv("MOEINF_AIO_THREADS");
-    g->aio.reset(new PrioAioPool(t ? atoi(t) : 4));
-  }
+  if (!g->aio) g->aio.reset(new PrioAioPool(g->knobs.aio_threads));
   return g->aio.get();
 }
 
@@ -1149,7 +1047,7 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   int64_t U = 0, rows = 0;
   for (int e = 0; e < E; ++e) { if (mirror[1 + e] > 0) { ++U; rows += mirror[1 + e]; } }
   const bool hidden = g->has_shared && local && g->last_form.hide_shared;  // the shared expert ran inside the router launches
-  const int64_t es = g->es, H = g->H, F = g->F, Fs = g->Fs, Tsh = (g->has_shared && local && !hidden) ? T : 0;
+  const int64_t es = g->es(), H = g->H, F = g->F, Fs = g->Fs, Tsh = (g->has_shared && local && !hidden) ? T : 0;
   // a self-routing forward carries the hidden shared expert's stage 2 inside the FFN stage-1 launch
   const bool sr2 = hidden && g->last_form.selfroute;
   if (hidden) g->prof.route_bytes += (sr2 ? 2 : 3) * Fs * H * es + (int64_t)T * ((sr2 ? 1 : 2) * Fs + (sr2 ? 1 : 2) * H) * es;
@@ -1158,13 +1056,13 @@ static void account_profile(moeinf_engine* g, const int32_t* mirror, int T, bool
   const bool gated = (et == MOEINF_EXPERT_MIXTRAL || et == MOEINF_EXPERT_DEEPSEEK || et == MOEINF_EXPERT_SWITCH_GATED);
   const bool bias = (et == MOEINF_EXPERT_NLLB || et == MOEINF_EXPERT_FSGPT);
   // bytes of one routed weight matrix in its slot's format (fp8 slots: 1 byte per weight; MXFP4 slots: codes and scales, 17/32)
-  const int64_t wm = g->slot_mx4 ? mx4_host_bytes(F, H) : F * H * (g->slot_f8 ? 1 : es);
+  const int64_t wm = g->slot_dt == DT_MX4 ? mx4_host_bytes(F, H) : F * H * dt_bytes(g->slot_dt);
   const int64_t b1 = U * ((gated ? 2 : 1) * wm + (bias ? F * es : 0)) + (Tsh ? 2 * Fs * H * es : 0) + (rows + Tsh) * H * es + rows * F * es + Tsh * Fs * es;
   const int64_t b2 = U * (wm + (bias ? H * es : 0)) + (Tsh ? H * Fs * es : 0) + rows * F * es + Tsh * Fs * es + (rows + Tsh) * H * es;
   g->prof.ffn1_bytes += b1;
   g->prof.ffn2_bytes += b2;
   if (local) {
-    g->prof.route_bytes += (int64_t)E * H * (g->cfg.gate_dtype == MOEINF_DTYPE_F32 ? 4 : 2) + (int64_t)T * H * es + (int64_t)T * E * 4 * 2 + (int64_t)T * K * 12;
+    g->prof.route_bytes += (int64_t)E * H * dt_bytes(g->gate_dt) + (int64_t)T * H * es + (int64_t)T * E * 4 * 2 + (int64_t)T * K * 12;
     g->prof.combine_bytes += (rows + Tsh) * H * es + (int64_t)T * H * es;
   }
   g->prof.forwards += 1;
@@ -1342,7 +1240,7 @@ static int ensure_resident(moeinf_engine* g, int layer, hipStream_t st, std::vec
       // a queued speculative transfer of this expert is overtaken by the demand (StartExec, task_scheduler.cpp:158-168)
       g->st.prefetch_cancelled += g->pq.remove_node(idx);
       // (one demand lane: a layer's misses dealt over TWO concurrent copy streams measured slower — DeepSeek-V2-Lite offload
-      // leg 27.9 -> 32.9 ms/token, 52.6 -> 44.2 GB/s, profiles/r06_offload_whole_blob_ab.txt: the streams share one link)
+      // leg 27.9 -> 32.9 ms/token, 52.6 -> 44.2 GB/s, round 6's whole-blob A/B under profiles/: the streams share one link)
       rc = issue_copy(g, idx, g->demand, true);
       if (rc != MOEINF_OK) break;
       g->demand_inflight.push_back(idx);
@@ -1597,7 +1495,7 @@ void make_route_args(const moeinf_engine* g, const void* x_dev, const void* gate
   memset(&ra, 0, sizeof ra);
   ra.x = x_dev; ra.gate_w = gate_w_dev; ra.logits = g->d_logits;
   ra.T = T; ra.H = g->H; ra.E = g->E; ra.K = g->K;
-  ra.x_dtype = g->dt; ra.gate_dtype = g->cfg.gate_dtype == MOEINF_DTYPE_BF16 ? DT_BF16 : (g->cfg.gate_dtype == MOEINF_DTYPE_F16 ? DT_F16 : DT_F32);
+  ra.x_dtype = g->dt; ra.gate_dtype = g->gate_dt;
   ra.kind = g->cfg.router_kind; ra.norm_topk_prob = g->cfg.norm_topk_prob; ra.scale = g->cfg.routed_scaling_factor;
   ra.no_renorm = g->route_no_renorm ? 1 : 0;
   ra.v3 = g->route_v3 ? 1 : 0;  // (e_bias: per layer, set by the callers that know the layer)
@@ -1623,7 +1521,7 @@ static LayerShape layer_shape(const moeinf_engine* g, int T, uint32_t flags, boo
   LayerShape s;
   s.router_kind = g->cfg.router_kind; s.expert_type = g->cfg.expert_type;
   s.dtype = g->dt; s.slot_dtype = g->slot_dt;
-  s.gate_dtype = g->cfg.gate_dtype == MOEINF_DTYPE_BF16 ? DT_BF16 : (g->cfg.gate_dtype == MOEINF_DTYPE_F16 ? DT_F16 : DT_F32);
+  s.gate_dtype = g->gate_dt;
   s.T = T; s.K = g->K; s.E = g->E; s.H = g->H; s.F = g->F; s.Fs = g->Fs;
   s.has_shared = g->has_shared ? 1 : 0; s.n_group = g->cfg.n_group; s.v3 = g->route_v3 ? 1 : 0;
   s.capacity = g->cfg.router_kind == MOEINF_ROUTER_SWITCH ? g->cfg.expert_capacity : 0;
@@ -1828,7 +1726,7 @@ extern "C" int moeinf_dispatch_mask_subset(moeinf_engine* g, int layer, const vo
   // the shared pseudo-expert is not part of a mask dispatch (the reference runs it in Python, deepseek.py:133-136)
   g->la_list.clear();  // (gate-lookahead predictions belong to the fused forward that made them)
   CHK(run_experts(g, layer, x_dev, st, nullptr, nullptr, nullptr));
-  if (rows > 0) HIPCHK(hipMemcpyAsync(y_dev, g->d_y, (size_t)rows * g->H * g->es, hipMemcpyDeviceToDevice, st));
+  if (rows > 0) HIPCHK(hipMemcpyAsync(y_dev, g->d_y, (size_t)rows * g->H * g->es(), hipMemcpyDeviceToDevice, st));
   g->last_T = tokens; g->last_layer = layer; g->last_stream = st;
   g->st.forwards += 1;
   CHK(end_forward(g, st, true));
@@ -1961,15 +1859,15 @@ extern "C" int moeinf_get_routing(moeinf_engine* g, int32_t* topk_idx, float* to
 extern "C" int moeinf_get_expert_outputs(moeinf_engine* g, void* host_out, int64_t nbytes) {
   CHK(sync_last(g));
   const int64_t rows = (int64_t)g->last_T * g->K + (g->has_shared ? g->last_T : 0);
-  const int64_t need = rows * g->H * g->es;
+  const int64_t need = rows * g->H * g->es();
   if (!host_out || nbytes > need || nbytes <= 0) return fail(MOEINF_ERR_INVALID, "nbytes must be in 1..%lld", (long long)need);
   if (g->has_shared && g->last_form.hide_shared) {
     // routed rows sit in y, the shared expert's rows (computed inside the router launches) in their own buffer
     int32_t routed = 0;
     HIPCHK(hipMemcpy(&routed, g->d_offsets + g->E, sizeof routed, hipMemcpyDeviceToHost));
-    const int64_t rb = std::min<int64_t>(nbytes, (int64_t)routed * g->H * g->es);
+    const int64_t rb = std::min<int64_t>(nbytes, (int64_t)routed * g->H * g->es());
     if (rb > 0) HIPCHK(hipMemcpy(host_out, g->d_y, (size_t)rb, hipMemcpyDeviceToHost));
-    if (nbytes > rb) HIPCHK(hipMemcpy((char*)host_out + rb, g->d_y_sh, (size_t)std::min<int64_t>(nbytes - rb, (int64_t)g->last_T * g->H * g->es), hipMemcpyDeviceToHost));
+    if (nbytes > rb) HIPCHK(hipMemcpy((char*)host_out + rb, g->d_y_sh, (size_t)std::min<int64_t>(nbytes - rb, (int64_t)g->last_T * g->H * g->es()), hipMemcpyDeviceToHost));
     return MOEINF_OK;
   }
   HIPCHK(hipMemcpy(host_out, g->d_y, (size_t)nbytes, hipMemcpyDeviceToHost));
@@ -2006,7 +1904,7 @@ static int pump_prefetch(moeinf_engine* g) {
     if (dn.slot >= 0 && dn.ready && hipEventQuery(dn.ready) != hipSuccess) { (void)hipGetLastError(); break; }
     g->demand_inflight.pop_front();
   }
-  while ((int)g->prefetch_inflight.size() < g->prefetch_window) {
+  while ((int)g->prefetch_inflight.size() < g->knobs.prefetch_window) {
     // an on-demand copy is on the link: a speculative copy started now would take half of its bandwidth away — the
     // queue keeps its tasks (they go stale with the layer counter if the pass moves on), the next pump tries again
     if (!g->demand_inflight.empty() && !g->draining) break;

@@ -21,7 +21,7 @@ static int ep_alloc(moeinf_engine* g, int cap_rows) {
   return MOEINF_OK;
 }
 
-static int64_t ep_row_elems(const moeinf_engine* g) { return g->H + 16 / g->es; }
+static int64_t ep_row_elems(const moeinf_engine* g) { return g->H + 16 / g->es(); }
 // fewest row slots per peer that can never overflow: a token sends a rank at most one row per expert that rank owns
 static int ep_min_cap(const moeinf_engine* g, int T) {
   const int per_rank = (g->E + g->cfg.ep_size - 1) / g->cfg.ep_size;
@@ -106,7 +106,7 @@ static int ep_route_pack_impl(moeinf_engine* g, int layer, const void* x_dev, in
   g->last_form.hide_shared = hide_shared;
   // the pack rides in the router's single-workgroup launch while the rows are few KB (one workgroup copies them)
   static const int fuse_kb = getenv("MOEINF_EP_FUSE_PACK_KB") ? atoi(getenv("MOEINF_EP_FUSE_PACK_KB")) : 64;
-  const bool fuse = np <= 64 && T <= 64 && (int64_t)np * g->H * g->es <= (int64_t)fuse_kb * 1024;
+  const bool fuse = np <= 64 && T <= 64 && (int64_t)np * g->H * g->es() <= (int64_t)fuse_kb * 1024;
   EpFuse pk;
   memset(&pk, 0, sizeof pk);
   pk.a.x = x_dev; pk.a.send = send_dev; pk.a.ld_send = ep_row_elems(g); pk.a.pair_pos = g->d_ep_pair_pos; pk.a.topk_idx = g->d_topk_idx;
@@ -183,8 +183,8 @@ static int ep_expert_ffn_rows(moeinf_engine* g, int layer, const void* recv_dev,
   IndexArgs ia;
   memset(&ia, 0, sizeof ia);
   // the expert id of every received row sits in the row's 16-byte tail
-  ia.topk_idx = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(recv_dev) + (size_t)g->H * g->es);
-  ia.idx_stride = (int)(ld * g->es / 4);
+  ia.topk_idx = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(recv_dev) + (size_t)g->H * g->es());
+  ia.idx_stride = (int)(ld * g->es() / 4);
   ia.pair_valid = nullptr; ia.T = nrows; ia.K = 1; ia.E = E; ia.rows = 1; ia.capacity = 0; ia.shared = 0;
   ia.counts = g->d_counts; ia.offsets = g->d_offsets; ia.active = g->d_active; ia.n_active = g->d_n_active;
   MirrorPlan mp;
@@ -352,11 +352,11 @@ extern "C" int moeinf_ep_comm_prepare(moeinf_engine* g, int cap_tokens) {
   if (g->ep_x_cap_rows == cap_rows && g->ep_x_send) return MOEINF_OK;  // prepared already
   if (g->ep_win.base && cap_rows != g->ep_win.cap_rows) return fail(MOEINF_ERR_STATE, "the peer-store window was built for another cap_tokens");
   ep_comm_free_buffers(g);
-  hipError_t e = hipMalloc(&g->ep_x_send, n * ep_row_elems(g) * g->es);
-  if (e == hipSuccess && !g->ep_x_recv) e = hipMalloc(&g->ep_x_recv, n * ep_row_elems(g) * g->es);
-  if (e == hipSuccess && !g->ep_x_y) e = hipMalloc(&g->ep_x_y, n * (size_t)g->H * g->es);
-  if (e == hipSuccess) e = hipMalloc(&g->ep_x_ret, n * (size_t)g->H * g->es);
-  if (e == hipSuccess) e = hipMemset(g->ep_x_y, 0, n * (size_t)g->H * g->es);  // padding rows travel as they are: keep them defined
+  hipError_t e = hipMalloc(&g->ep_x_send, n * ep_row_elems(g) * g->es());
+  if (e == hipSuccess && !g->ep_x_recv) e = hipMalloc(&g->ep_x_recv, n * ep_row_elems(g) * g->es());
+  if (e == hipSuccess && !g->ep_x_y) e = hipMalloc(&g->ep_x_y, n * (size_t)g->H * g->es());
+  if (e == hipSuccess) e = hipMalloc(&g->ep_x_ret, n * (size_t)g->H * g->es());
+  if (e == hipSuccess) e = hipMemset(g->ep_x_y, 0, n * (size_t)g->H * g->es());  // padding rows travel as they are: keep them defined
   if (e != hipSuccess) { ep_comm_free_buffers(g); (void)hipGetLastError(); return fail(MOEINF_ERR_HIP, "exchange buffers: %s", hipGetErrorString(e)); }
   g->ep_cap_tokens = cap_tokens;
   g->ep_x_cap_rows = cap_rows;
@@ -415,12 +415,12 @@ extern "C" int moeinf_ep_peer_export(moeinf_engine* g, int cap_tokens, void* blo
     *g->ep_err_host = 0;
     if (const char* ev = getenv("MOEINF_EP_ERR_CHECK_EVERY")) g->ep_err_every = (uint32_t)std::max(1, atoi(ev));
   }
-  std::string err = g->ep_win.create(g->cfg.ep_size, cap_rows, ep_row_elems(g) * g->es, (int64_t)g->H * g->es, g->E);
+  std::string err = g->ep_win.create(g->cfg.ep_size, cap_rows, ep_row_elems(g) * g->es(), (int64_t)g->H * g->es(), g->E);
   if (err.empty() && !g->ep_x_recv) {  // routed-form staging of the broadcast form's slow path (launch_ep_bcast_unpack)
-    if (hipMalloc(&g->ep_x_recv, n * ep_row_elems(g) * g->es) != hipSuccess) { g->ep_x_recv = nullptr; err = "hipMalloc of the unpack staging buffer failed"; }
+    if (hipMalloc(&g->ep_x_recv, n * ep_row_elems(g) * g->es()) != hipSuccess) { g->ep_x_recv = nullptr; err = "hipMalloc of the unpack staging buffer failed"; }
   }
   if (err.empty() && !g->ep_x_y) {  // staging of the owner's outputs on the generic path (more rows than the self-indexing kernels take)
-    if (hipMalloc(&g->ep_x_y, n * (size_t)g->H * g->es) != hipSuccess) { g->ep_x_y = nullptr; err = "hipMalloc of the output staging buffer failed"; }
+    if (hipMalloc(&g->ep_x_y, n * (size_t)g->H * g->es()) != hipSuccess) { g->ep_x_y = nullptr; err = "hipMalloc of the output staging buffer failed"; }
   }
   EpPeerBlob b;
   if (err.empty()) err = g->ep_win.export_blob(g->cfg.ep_rank, g->cfg.ep_size, g->cfg.device_id, &b);
@@ -703,12 +703,12 @@ extern "C" int moeinf_ep_moe_forward(moeinf_engine* g, int layer, const void* x_
   mark(0);
   CHK(moeinf_ep_route_pack(g, layer, x_dev, tokens, batch_rows, gate_w_dev, g->ep_x_send, nullptr, cap, stream));
   mark(1);
-  std::string err = rccl_all_to_all(api, g->ep_comm, G, g->ep_x_send, g->ep_x_recv, (size_t)cap * ep_row_elems(g) * g->es, st);
+  std::string err = rccl_all_to_all(api, g->ep_comm, G, g->ep_x_send, g->ep_x_recv, (size_t)cap * ep_row_elems(g) * g->es(), st);
   if (!err.empty()) return fail(MOEINF_ERR_HIP, "dispatch all-to-all: %s", err.c_str());
   mark(2);
   CHK(moeinf_ep_expert_ffn(g, layer, g->ep_x_recv, g->ep_x_y, cap, stream));
   mark(3);
-  err = rccl_all_to_all(api, g->ep_comm, G, g->ep_x_y, g->ep_x_ret, (size_t)cap * g->H * g->es, st);
+  err = rccl_all_to_all(api, g->ep_comm, G, g->ep_x_y, g->ep_x_ret, (size_t)cap * g->H * g->es(), st);
   if (!err.empty()) return fail(MOEINF_ERR_HIP, "combine all-to-all: %s", err.c_str());
   mark(4);
   CHK(moeinf_ep_combine(g, x_dev, g->ep_x_ret, out_dev, cap, stream));

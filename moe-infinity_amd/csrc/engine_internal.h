@@ -38,6 +38,7 @@
 #include "offload_store.h"
 #include "prefetch_queue.h"
 #include "tracer.h"
+#include "transfer_plan.h"
 
 using namespace moeinf;
 
@@ -83,75 +84,6 @@ struct DeviceScope {
     if (r_ != MOEINF_OK) return r_; \
   } while (0)
 
-static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-static constexpr int64_t kAioAlignment = 4096;  // core/aio/archer_aio_utils.h kAioAlignment (model_topology.cpp:429-431)
-
-// ------------------------------------------------------------------------------------------------
-// blob layout
-// ------------------------------------------------------------------------------------------------
-struct BlobLayout {
-  int n = 0;
-  int64_t off[4] = {0, 0, 0, 0}, size[4] = {0, 0, 0, 0};
-  int64_t total = 0;
-};
-// mx4: the routed experts of an MXFP4-slot engine — every matrix is ONE tensor, its packed e2m1 codes [R, K/2] followed by its e8m0
-// scales [R, K/32] (include/moeinf.h); gated families only (moeinf_create_ex refuses the others)
-static BlobLayout make_layout(int expert_type, int64_t H, int64_t F, int64_t es, bool mx4 = false) {
-  BlobLayout b;
-  auto add = [&](int64_t bytes) {
-    b.off[b.n] = b.total;
-    b.size[b.n] = bytes;
-    b.total += align_up(bytes, kAioAlignment);
-    ++b.n;
-  };
-  switch (expert_type) {
-    case MOEINF_EXPERT_MIXTRAL:   // w1[F,H] w2[H,F] w3[F,H]
-    case MOEINF_EXPERT_DEEPSEEK:  // gate[F,H] up[F,H] down[H,F]
-    case MOEINF_EXPERT_SWITCH_GATED:  // wi_0[F,H] wi_1[F,H] wo[H,F] (expert_module.cpp:46-52)
-      if (mx4) { add(mx4_host_bytes(F, H)); add(mx4_host_bytes(F, H)); add(mx4_host_bytes(F, H)); break; }  // (= mx4_host_bytes(H, F))
-      add(F * H * es); add(F * H * es); add(F * H * es);
-      break;
-    case MOEINF_EXPERT_NLLB:
-    case MOEINF_EXPERT_FSGPT:  // fc1.w fc1.b fc2.w fc2.b
-      add(F * H * es); add(F * es); add(H * F * es); add(H * es);
-      break;
-    case MOEINF_EXPERT_SWITCH:  // wi wo
-      add(F * H * es); add(H * F * es);
-      break;
-    default: break;
-  }
-  return b;
-}
-
-// Device-side (HBM slot) layout: matrices in MFMA-tile order (kernels.hip), biases raw; 4 KiB aligned.  dt / es: the SLOT's
-// element (DT_F8 / 1 for fp8 slots: 64 k per 1-KiB tile, half of bf16's bytes; DT_MX4 for MXFP4 slots: 128 k per 1-KiB code tile and
-// the matrix's scale dwords behind its code tiles, kernels.h tiled_bytes)
-struct DevLayout {
-  int n = 0;
-  int64_t off[4] = {0, 0, 0, 0}, size[4] = {0, 0, 0, 0};
-  int R[4] = {0, 0, 0, 0}, K[4] = {0, 0, 0, 0};  // K == 0: not a matrix (bias vector, copied as is)
-  int64_t total = 0;
-};
-static DevLayout make_dev_layout(int expert_type, int64_t H, int64_t F, int dt, int64_t es) {
-  DevLayout d;
-  auto mat = [&](int64_t R, int64_t K) {
-    d.off[d.n] = d.total; d.R[d.n] = (int)R; d.K[d.n] = (int)K; d.size[d.n] = tiled_bytes(R, K, dt);
-    d.total += align_up(d.size[d.n], kAioAlignment); ++d.n;
-  };
-  auto vec = [&](int64_t n) {
-    d.off[d.n] = d.total; d.R[d.n] = (int)n; d.K[d.n] = 0; d.size[d.n] = n * es;
-    d.total += align_up(d.size[d.n], kAioAlignment); ++d.n;
-  };
-  switch (expert_type) {
-    case MOEINF_EXPERT_MIXTRAL: mat(F, H); mat(H, F); mat(F, H); break;
-    case MOEINF_EXPERT_DEEPSEEK: case MOEINF_EXPERT_SWITCH_GATED: mat(F, H); mat(F, H); mat(H, F); break;
-    case MOEINF_EXPERT_NLLB: case MOEINF_EXPERT_FSGPT: mat(F, H); vec(F); mat(H, F); vec(H); break;
-    case MOEINF_EXPERT_SWITCH: mat(F, H); mat(H, F); break;
-    default: break;
-  }
-  return d;
-}
-
 // ------------------------------------------------------------------------------------------------
 // engine
 // ------------------------------------------------------------------------------------------------
@@ -186,6 +118,7 @@ struct Slot {
 
 static constexpr int kFenceRing = 64;
 static constexpr int kMirrorPool = 128;  // pooled pinned routing mirrors of sync-free forwards not yet applied to the counters
+static_assert(MoverKnobs::kMaxFenceEvery == kMirrorPool / 4, "a fence at least every quarter of the mirror pool");
 
 // One H2D lane = a copy stream (hipMemcpyAsync, served by an SDMA engine) + a re-tile stream (kernels) + a ring of two
 // staging buffers, each large enough for the biggest tensor of a blob.  Tensor i+1 is copied into the other
@@ -206,24 +139,21 @@ struct CopyLane {
 
 constexpr int kLaTokens = 8;  // the lookahead route runs for decode-sized forwards only
 struct moeinf_engine {
-  moeinf_config cfg;
-  int64_t es = 2;  // element size
-  int dt = DT_BF16;
+  moeinf_config cfg;  // as the caller gave it, but router_kind (route_v3, route_no_renorm); its dtypes are read through the four below
+  // weight_format's answer (transfer_plan.h): dt arithmetic, activations and the shared expert; host_dt / slot_dt the routed experts'
+  // host blob / HBM slot (dt, DT_F8 or DT_MX4); gate_dt the gate weight
+  int dt = DT_BF16, host_dt = DT_BF16, slot_dt = DT_BF16, gate_dt = DT_BF16;
+  int64_t es() const { return dt_bytes(dt); }  // bytes of an activation element
+  MoverKnobs knobs;   // the tier mover's environment, as it was when the engine was created
+  TransferPlan plan;  // how every routed expert travels host -> slot (issue_copy executes it)
   BlobLayout lay, lay_sh;   // host blob (reference layout)
   DevLayout dlay, dlay_sh;  // HBM slot (tiled)
   CopyLane demand, prefetch;  // on-demand misses (high priority) / speculative copies (low priority)
-  int64_t stage_bytes = 0;
-  // Small experts travel as ONE hipMemcpyAsync of the whole contiguous host blob (as the reference copies it,
-  // model_topology.cpp:102-119) into a staging buffer sized for an expert, re-tiled by one launch; big ones (Mixtral: 336 MiB)
-  // tensor by tensor, so FFN stage 1 can start while the down projection is still on the link.
-  bool whole_blob = false;
   unsigned long long* d_copy_ts = nullptr;  // [kCopyTsRing][4] timing records of the pull form (kernels.hip: pull_retile_kernel)
   std::vector<uint64_t> copy_ts_expect;     // per ring slot: finished-workgroup count that means "this use of the slot is complete" (grows)
   uint64_t copy_ts_head = 0, copy_ts_tail = 0;
   uint64_t copy_seq = 0;
   unsigned long long copy_busy_until = 0;   // tick up to which link-busy time has been accounted
-  bool h2d_pull = false;   // experts are PULLED by a kernel of the copy stream straight from the pinned host blob into the tiled slot
-  int h2d_pull_wgs = 16;
   // next-layer gate lookahead (moeinf_set_lookahead)
   std::vector<const void*> la_gates;   // [L] borrowed device pointers; empty: off
   int la_max = 0;
@@ -235,11 +165,6 @@ struct moeinf_engine {
   std::vector<int> la_list;            // node indices predicted for the next layer, best first
   int num_cus = 0;                     // of THIS engine's device
   int layer1_switch_wgs_per_cu = -1;   // occupancy of the one-launch Switch kernel (asked once per engine)
-  bool host_f8 = false;                // dtype id 3: fp8 (e4m3fn) experts in the host tier, bf16 slots and arithmetic
-  bool slot_mx4 = false;               // MXFP4 slots (moeinf_create_ex, MOEINF_SLOT_MXFP4): a bf16 engine whose routed experts are MXFP4 in the host tier AND in HBM
-  bool slot_f8 = false;                // ... and fp8 slots (moeinf_create_ex): routed experts stay e4m3fn in HBM, bf16 arithmetic
-  int slot_dt = DT_BF16;               // dtype of the routed experts' slots (DT_F8 with slot_f8, DT_MX4 with slot_mx4, else dt)
-  int64_t host_es = 2;                 // bytes per element of the HOST blob (1 with host_f8, else es)
   bool route_v3 = false;               // MOEINF_ROUTER_DEEPSEEK_V3: cfg.router_kind is stored as DEEPSEEK
   std::vector<const float*> gate_bias; // ... per layer: e_score_correction_bias (borrowed device pointers)
   bool route_no_renorm = false;        // MOEINF_ROUTER_SOFTMAX_TOPK (Grok / Arctic): cfg.router_kind is stored as MIXTRAL
@@ -278,14 +203,13 @@ struct moeinf_engine {
   float gov_score = 1.f;              // exponential average of outcomes (1 = dispatched before eviction, 0 = evicted unused)
   int gov_outcomes = 0, gov_skipped = 0;
   std::deque<int> prefetch_inflight;  // node indices whose copy was issued on the prefetch lane, oldest first
-  int prefetch_window = 2;            // experts in flight on the prefetch lane at most
   std::vector<void*> host_free;       // arena blocks returned by host-tier eviction
   uint64_t host_clock = 0;
 
   // streams / events
   hipEvent_t route_ev = nullptr;
   // fences: an event on the compute stream after forward #fence_seq[i].  Recorded after EVERY forward that took the decision path
-  // (copies follow, and they should wait for no more compute than they must) but only after every fence_every-th sync-free
+  // (copies follow, and they should wait for no more compute than they must) but only after every knobs.fence_every-th sync-free
   // forward (a record between two kernels costs the stream 2.7-4 us: profiles/r06_fence_every.md); whoever needs a forward that
   // no fence covers yet records one then (fence_for)
   hipEvent_t fence_ev[kFenceRing];
@@ -293,7 +217,6 @@ struct moeinf_engine {
   uint64_t fence_head = 0;   // fences recorded so far (ring position = fence_head % kFenceRing)
   uint64_t fenced_seq = 0;   // the newest forward a recorded fence covers
   hipStream_t unfenced_stream = nullptr;  // the stream the forwards after fenced_seq were launched on
-  int fence_every = 16;
   uint64_t seq = 0;  // forwards issued
   std::vector<std::pair<hipEvent_t, hipEvent_t>> copy_timers;  // (start, end) pairs not yet accumulated
   std::vector<std::pair<hipEvent_t, hipEvent_t>> wait_timers;  // compute-stream stalls on copies
@@ -438,7 +361,7 @@ static inline int end_forward(moeinf_engine* g, hipStream_t st, bool must) {
   if (g->fenced_seq < g->seq && g->unfenced_stream != st) CHK(record_fence(g, g->unfenced_stream));
   g->seq += 1;
   g->unfenced_stream = st;
-  if (must || g->seq - g->fenced_seq >= (uint64_t)g->fence_every) CHK(record_fence(g, st));
+  if (must || g->seq - g->fenced_seq >= (uint64_t)g->knobs.fence_every) CHK(record_fence(g, st));
   return MOEINF_OK;
 }
 
