@@ -149,12 +149,14 @@ int moeinf_rows_estimate(int tokens, int top_k, int num_experts);
  * for an FFN stage.  One function decides for every dtype (csrc/kernels.h ffn_form); these exports report
  * what it gives, with the environment knobs as they are at the call (the launcher reads them once per process).
  * dtype: MOEINF_DTYPE_*, MOEINF_DTYPE_F8E4M3 = an fp8 slot (bf16 activations, fp8 routed weights), MOEINF_SLOT_MXFP4 = an MXFP4
- * slot (bf16 activations, MXFP4 routed weights: the row kernel at every row count, K % 128 == 0); epi: the stage's epilogue
+ * slot (bf16 activations, MXFP4 routed weights, K % 128 == 0: the row kernel at every row count unless flags bit 3 is set); epi: the stage's epilogue
  * (csrc/kernels.h EPI_*: 0 none, 1 bias, 2 relu, 3 bias + relu, 4 gated SiLU, 5 gated GELU; 4 and 5 are the gated stage);
  * K / K_sh: reduction length of the routed / shared experts (K_sh = 0: no shared expert rides in the launch); R: output rows
  * (the larger of the routed and the shared expert's); active: experts with rows (the grid's upper bound); max_rows: rows of the
  * busiest expert as the engine passes it (1.5 x the mean + 1 on the sync-free path); num_cus: compute units; flags: bit 0
- * ld_out % 8 != 0, bit 1 rows_bound * ld_in does not fit in 32 bits, bit 2 the stage fuses the combine.
+ * ld_out % 8 != 0, bit 1 rows_bound * ld_in does not fit in 32 bits, bit 2 the stage fuses the combine, bit 3 (value 8) the engine
+ * has MXFP4 grouped GEMMs switched on (moeinf_set_mxfp4_gemm; read only for dtype == MOEINF_SLOT_MXFP4: above 16 rows per expert
+ * ffn_gemm_hyb up to 128 / 64 rows, ffn_gemm_lds beyond, never ring2 or big; with the bit clear every answer is what it was).
  * out[0]: -1 = no kernel (an fp8 stage the kernels do not take), 0 = the row kernel, 1 = ffn_gemm_hyb, 2 = ffn_gemm_lds,
  * 3 = ffn_gemm_ring2, 4 = ffn_gemm (register GEMM), 5 = ffn_gemm_big; out[1]: waves per workgroup; out[2]: unroll (row kernel);
  * out[3]: token groups of 16 per pass (row kernel, register GEMM); out[4]: row groups per wave (hyb); out[5]: k-tiles per stage
@@ -235,8 +237,9 @@ int moeinf_destroy(moeinf_engine* eng);
  * shared expert stays bf16 (its blob and moeinf_register_shared are a bf16 engine's).  Accepted for Mixtral / DeepSeek experts
  * under the routers fp8 slots accept, ep_size == 1, hidden % 128 == 0, inter % 128 == 0 (and reductions the tier mover's scale units
  * hold: up to 8192, 16384 with K/128 even, 32768 with K/128 a multiple of 4), with the pull tier mover (not MOEINF_H2D_PULL=0);
- * anything else is MOEINF_ERR_UNSUPPORTED with a message that names mxfp4 and the reason.  Every row count runs the row kernel
- * (four token tiles per pass above 16 rows per expert); MXFP4 forms of the grouped GEMMs are not built. */
+ * anything else is MOEINF_ERR_UNSUPPORTED with a message that names mxfp4 and the reason.  By default every row count runs the row
+ * kernel (four token tiles per pass above 16 rows per expert); moeinf_set_mxfp4_gemm switches the MXFP4 forms of the hybrid and the
+ * LDS-staged grouped GEMM on for stages with more rows (MXFP4 forms of ring2 and the 256 x 256 kernel are not built). */
 typedef struct moeinf_create_options {
   int32_t struct_bytes;
   int32_t slot_dtype;
@@ -245,6 +248,14 @@ typedef struct moeinf_create_options {
 int moeinf_create_ex(const moeinf_config* cfg, const moeinf_create_options* opts, moeinf_engine** out);
 /* the dtype the engine's HBM expert slots hold (MOEINF_DTYPE_*) */
 int moeinf_slot_dtype(const moeinf_engine* eng, int32_t* slot_dtype);
+/* MXFP4-slot engines: on != 0 = FFN stages with more than 16 rows per expert take the MXFP4 forms of the grouped GEMMs (ffn_gemm_hyb,
+ * ffn_gemm_lds; moeinf_ffn_form with flags bit 3) from the next forward on; 0 = the row kernel at every row count, the state after
+ * create.  Host state only: nothing is enqueued.  MOEINF_ERR_INVALID for a NULL engine, MOEINF_ERR_UNSUPPORTED (the message names
+ * mxfp4) when the engine's slots are not MXFP4. */
+int moeinf_set_mxfp4_gemm(moeinf_engine* eng, int on);
+/* The kernel ids (moeinf_ffn_form's out[0]) that stage 1 (out2[0]) and stage 2 (out2[1]) of the engine's most recent forward took
+ * through launch_ffn_stage; -2 where that stage ran a decode launcher or did not run. */
+int moeinf_last_ffn_forms(const moeinf_engine* eng, int32_t out2[2]);
 
 /* ---- expert blobs --------------------------------------------------------------------------
  * The reference keeps one contiguous, 4 KiB-aligned blob per expert with the tensors in

@@ -97,6 +97,8 @@ PROTOTYPES = {
     "moeinf_create": (C.c_int, [C.POINTER(Config), C.POINTER(_P)]),
     "moeinf_create_ex": (C.c_int, [C.POINTER(Config), C.POINTER(CreateOptions), C.POINTER(_P)]),
     "moeinf_slot_dtype": (C.c_int, [_P, _I32P]),
+    "moeinf_set_mxfp4_gemm": (C.c_int, [_P, C.c_int]),
+    "moeinf_last_ffn_forms": (C.c_int, [_P, _I32P]),
     "moeinf_destroy": (C.c_int, [_P]),
     "moeinf_expert_layout": (C.c_int, [_P, C.c_int, _I64P, _I64P, _I32P, _I64P]),
     "moeinf_register_expert": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),

@@ -89,10 +89,16 @@ class EngineConfig:
     # host tier, on the link and in their HBM slots (moeinf_create_ex, MOEINF_SLOT_MXFP4): y = FFN(x; dequant(W).to(bf16)).  Mixtral /
     # DeepSeek experts, ep_size 1, hidden and inter multiples of 128.  Not part of the C config struct.
     mxfp4_slots: bool = False
+    # with mxfp4_slots: FFN stages with more than 16 rows per expert (prefill, large batches) take the MXFP4 forms of the hybrid and the
+    # LDS-staged grouped GEMM instead of the row kernel (moeinf_set_mxfp4_gemm; MoEEngine.set_mxfp4_gemm switches it at run time).  Off
+    # by default: the default selection is what it was.  Not part of the C config struct.
+    mxfp4_gemm: bool = False
 
     def __post_init__(self):
         if self.fp8_slots and self.mxfp4_slots:
             raise ValueError("fp8_slots and mxfp4_slots are two different slot formats: set one")
+        if self.mxfp4_gemm and not self.mxfp4_slots:
+            raise ValueError("mxfp4_gemm switches the grouped GEMMs of MXFP4 slots on: set mxfp4_slots too")
 
     def to_dict(self):
         return asdict(self)

@@ -80,7 +80,9 @@ static moeinf::FfnForm ffn_form_of(int dtype, int epi, int K, int K_sh, int R, i
   s.dtype = (f8w || mx4w) ? moeinf::DT_BF16 : dtype; s.wdtype = f8w ? moeinf::DT_F8 : (mx4w ? moeinf::DT_MX4 : dtype);
   s.epi = epi; s.K = K; s.R = R; s.K_sh = K_sh; s.R_sh = K_sh > 0 ? R : 0;
   s.ld_in = 1; s.ld_out = (flags & 1) ? 4 : 8; s.rows_bound = (flags & 2) ? int64_t(1) << 32 : 0; s.fuse_combine = (flags & 4) ? 1 : 0;
-  return moeinf::ffn_form(moeinf::ffn_shape(s), active, max_rows, num_cus, moeinf::FfnKnobs::from_env());
+  moeinf::FfnShape h = moeinf::ffn_shape(s);
+  h.mx4_gemm = (flags & 8) != 0;
+  return moeinf::ffn_form(h, active, max_rows, num_cus, moeinf::FfnKnobs::from_env());
 }
 
 extern "C" int moeinf_ffn_form(int dtype, int epi, int K, int K_sh, int R, int active, int max_rows, int num_cus, int flags, int32_t* out14) {
@@ -1365,10 +1367,10 @@ static int run_experts(moeinf_engine* g, int layer, const void* x_in, hipStream_
     // then pick the same kernel form unless the routing is skewed beyond 1.5 x the mean
     int max_rows = rows_hint;
     for (int i = a; i < b; ++i) max_rows = std::max(max_rows, (int)g->h_mirror[1 + active[i]]);
-    HIPCHK(launch_ffn_stage(s1, b - a, max_rows, g->num_cus, st));
+    HIPCHK(launch_ffn_stage(s1, b - a, max_rows, g->num_cus, st, g->mx4_gemm, &g->last_ffn_forms[0]));
     if (ev_mid && b == na) HIPCHK(hipEventRecord(ev_mid, st));
     CHK(wait_late(g, layer, st, late));  // stage 2 reads the down projections: wait for the rest of each transfer
-    HIPCHK(launch_ffn_stage(s2, b - a, max_rows, g->num_cus, st));
+    HIPCHK(launch_ffn_stage(s2, b - a, max_rows, g->num_cus, st, g->mx4_gemm, &g->last_ffn_forms[1]));
     if (la_now && !la_early) CHK(lookahead_issue(g, layer));
     a = b;
     if (a < na) CHK(end_forward(g, st, true));
@@ -1434,7 +1436,7 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
       case ST_FRONT1: le = launch_moe_front1(*sr->ra, *sr->ia, sr->sh1, sr->sh2, s1, sy, lf.sr, st); break;
       case ST_SELFROUTE_MULTI: le = launch_ffn1_selfroute_multi(*sr->ra, *sr->ia, s1, sr->sh2, std::min(E, T * g->K), lf.sr, st); break;
       case ST_SELFROUTE: le = launch_ffn1_selfroute(*sr->ra, *sr->ia, s1, sr->sh2, lf.sr, st); break;
-      case ST_GENERIC: le = launch_ffn_stage(s1, max_active, exp_rows, g->num_cus, st); break;
+      case ST_GENERIC: le = launch_ffn_stage(s1, max_active, exp_rows, g->num_cus, st, g->mx4_gemm, &g->last_ffn_forms[0]); break;
     }
     disarm_kernel_timer();  // (after a launch that failed before taking it)
     HIPCHK(le);
@@ -1446,7 +1448,8 @@ int dispatch_experts(moeinf_engine* g, int layer, const void* x_in, int64_t ld_x
     }
     if (prof && !kt1) HIPCHK(hipEventRecord(pr->ev[3], st));
     if (kt2 && (pr->k2 = get_event(g))) arm_kernel_timer(pr->k2, pr->ev[4]);
-    le = lf.stage2 == ST_DECODE1 ? launch_ffn2_decode1(s2, lf.dec1, st) : launch_ffn_stage(s2, max_active, exp_rows, g->num_cus, st);
+    le = lf.stage2 == ST_DECODE1 ? launch_ffn2_decode1(s2, lf.dec1, st)
+                                 : launch_ffn_stage(s2, max_active, exp_rows, g->num_cus, st, g->mx4_gemm, &g->last_ffn_forms[1]);
     disarm_kernel_timer();
     HIPCHK(le);
     if (prof && !(kt2 && pr->k2)) HIPCHK(hipEventRecord(pr->ev[4], st));
@@ -1595,6 +1598,7 @@ static int moe_forward(moeinf_engine* g, int layer, const void* x_dev, int token
   strace.mark("set_device");
   hipStream_t st = (hipStream_t)stream;
   const int T = tokens, K = g->K, E = g->E;
+  g->last_ffn_forms[0] = g->last_ffn_forms[1] = -2;  // (moeinf_last_ffn_forms: a stage that runs a decode launcher, or not at all)
 
   RouteArgs ra;
   make_route_args(g, x_dev, gate_w_dev, T, ra);
@@ -1776,6 +1780,19 @@ extern "C" int moeinf_copy_routing_dev(moeinf_engine* g, float* logits_dev, int3
   // capacity-dropped / unrouted pairs are reported as -1, like moeinf_get_routing does on the host
   if (topk_idx_dev) HIPCHK(launch_masked_idx(g->d_topk_idx, g->d_pair_valid, topk_idx_dev, (int)(T * g->K), st));
   if (topk_w_dev) HIPCHK(hipMemcpyAsync(topk_w_dev, g->d_topk_w, T * g->K * 4, hipMemcpyDeviceToDevice, st));
+  return MOEINF_OK;
+}
+
+// host state only: the next forward's launch_ffn_stage calls read it
+extern "C" int moeinf_set_mxfp4_gemm(moeinf_engine* g, int on) {
+  if (!g) return fail(MOEINF_ERR_INVALID, "engine is NULL");
+  if (g->slot_dt != DT_MX4) return fail(MOEINF_ERR_UNSUPPORTED, "moeinf_set_mxfp4_gemm: the engine's slots are not mxfp4");
+  g->mx4_gemm = on != 0;
+  return MOEINF_OK;
+}
+extern "C" int moeinf_last_ffn_forms(const moeinf_engine* g, int32_t out2[2]) {
+  if (!g || !out2) return fail(MOEINF_ERR_INVALID, "engine or out2 is NULL");
+  out2[0] = g->last_ffn_forms[0]; out2[1] = g->last_ffn_forms[1];
   return MOEINF_OK;
 }
 

@@ -143,6 +143,8 @@ struct moeinf_engine {
   // weight_format's answer (transfer_plan.h): dt arithmetic, activations and the shared expert; host_dt / slot_dt the routed experts'
   // host blob / HBM slot (dt, DT_F8 or DT_MX4); gate_dt the gate weight
   int dt = DT_BF16, host_dt = DT_BF16, slot_dt = DT_BF16, gate_dt = DT_BF16;
+  bool mx4_gemm = false;          // moeinf_set_mxfp4_gemm: MXFP4 stages with many rows take the grouped GEMMs (ffn_form)
+  int last_ffn_forms[2] = {-2, -2};  // moeinf_last_ffn_forms: the FFN_* ids of the last forward's two launch_ffn_stage calls (-2: none)
   int64_t es() const { return dt_bytes(dt); }  // bytes of an activation element
   MoverKnobs knobs;   // the tier mover's environment, as it was when the engine was created
   TransferPlan plan;  // how every routed expert travels host -> slot (issue_copy executes it)

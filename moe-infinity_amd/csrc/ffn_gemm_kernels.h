@@ -14,6 +14,9 @@ namespace moeinf {
 // fp8-slot bodies (T = f8w_t): ffn_gemm_f8_kernels.h
 template <int NMAT, int RGB, int NWV, bool XL> __device__ __forceinline__ void ffn_gemm_lds_kernel_f8w(const FfnStage& s);
 template <int NMAT, int RW, int KK, bool XL> __device__ __forceinline__ void ffn_gemm_hyb_kernel_f8w(const FfnStage& s);
+// MXFP4-slot bodies (T = mx4w_t): ffn_gemm_mx4_kernels.h
+template <int NMAT, int RGB, int NWV, bool XL> __device__ __forceinline__ void ffn_gemm_lds_kernel_mx4w(const FfnStage& s);
+template <int NMAT, int RW, int KK, bool XL> __device__ __forceinline__ void ffn_gemm_hyb_kernel_mx4w(const FfnStage& s);
 
 // ------------------------------------------------------------------------------------------------
 // ffn_gemm: the same stage for experts with MANY tokens (prefill, large batches) — a register-tiled
@@ -191,6 +194,8 @@ template <typename T, int NMAT, int RGB, int NWV, bool XL>
 __global__ __launch_bounds__(NWV * 64) void ffn_gemm_lds_kernel(FfnStage s) {
   if constexpr (std::is_same<T, f8w_t>::value) {  // fp8 slots (ffn_gemm_f8_kernels.h, built by ffn_gemm_f8.hip)
     ffn_gemm_lds_kernel_f8w<NMAT, RGB, NWV, XL>(s);
+  } else if constexpr (std::is_same<T, mx4w_t>::value) {  // MXFP4 slots (ffn_gemm_mx4_kernels.h, built by ffn_gemm_mx4.hip)
+    ffn_gemm_lds_kernel_mx4w<NMAT, RGB, NWV, XL>(s);
   } else {
   constexpr int EPV = DT<T>::EPV;
   constexpr int EPT = 4 * EPV;
@@ -371,6 +376,8 @@ template <typename T, int NMAT, int RW, int KK, bool XL>
 __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
   if constexpr (std::is_same<T, f8w_t>::value) {  // fp8 slots (ffn_gemm_f8_kernels.h, built by ffn_gemm_f8.hip)
     ffn_gemm_hyb_kernel_f8w<NMAT, RW, KK, XL>(s);
+  } else if constexpr (std::is_same<T, mx4w_t>::value) {  // MXFP4 slots (ffn_gemm_mx4_kernels.h, built by ffn_gemm_mx4.hip)
+    ffn_gemm_hyb_kernel_mx4w<NMAT, RW, KK, XL>(s);
   } else {
   static_assert(!XL || KK % 2 == 0, "full-line staging moves k-tiles in pairs");
   constexpr int EPV = DT<T>::EPV;
@@ -522,7 +529,8 @@ __global__ __launch_bounds__(256) void ffn_gemm_hyb_kernel(FfnStage s) {
 }
 
 // the hybrid, LDS-staged or register GEMM in the form ffn_form chose; instantiated by ffn_gemm.hip (bf16, fp32), ffn_gemm_f16.hip
-// and ffn_gemm_f8.hip (fp8 slots: no register GEMM)
+// and ffn_gemm_f8.hip (fp8 slots: no register GEMM); the MXFP4 slots' forms (full-line staging only) have a launcher of their own in
+// ffn_gemm_mx4.hip
 template <typename T, int NMAT>
 void launch_ffn_gemm_t(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st) {
   if (f.kernel == FFN_HYB) {  // weights -> registers, activations -> LDS

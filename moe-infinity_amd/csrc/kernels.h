@@ -144,12 +144,12 @@ struct FfnKnobs {
   int use_gemm = 2;        // MOEINF_FFN_GEMM: 0 = the row kernel's four-token-tile form, 1 = the register GEMM, 2 = by rows, 3 = hybrid
   int gemm_nt = 0;         // MOEINF_FFN_GEMM_NT: token groups per pass of the register GEMM (0: 4)
   int rgb_plain = 0;       // MOEINF_FFN_GEMM_RGB: row groups per LDS-kernel workgroup, plain stage (0: by the rule in ffn_form)
-  int rgb_gated = 4;       // MOEINF_FFN_GEMM_RGB2: ... gated stage
+  int rgb_gated = 4;       // MOEINF_FFN_GEMM_RGB2: ... gated stage (MXFP4: always 4, the 128-row gated forms are not built)
   int big = 1;             // MOEINF_GEMM_BIG: 0 = never the 256 x 256 kernel
   int big_rows = 256;      // MOEINF_GEMM_BIG_ROWS: the 256 x 256 kernel above
   int hyb_rows = 0;        // MOEINF_GEMM_HYB_ROWS (0: 128 with <= 16 active experts, else 64)
-  int hyb_kk = 4;          // MOEINF_GEMM_HYB_KK: k-tiles per stage of the hybrid kernel (2 or 4)
-  int xl = 1;              // MOEINF_GEMM_XL: full-line activation staging (hybrid, LDS)
+  int hyb_kk = 4;          // MOEINF_GEMM_HYB_KK: k-tiles per stage of the hybrid kernel (2 or 4; MXFP4: always 4 = one code tile)
+  int xl = 1;              // MOEINF_GEMM_XL: full-line activation staging (hybrid, LDS); an MXFP4 stage keeps it under 0 (only those forms are built)
   int wide = -1;           // MOEINF_GEMM_WIDE: the LDS kernel's 8 waves (-1: above 128 rows)
   int ring2_bits = 3;      // MOEINF_GEMM_RING2: bit 0 gated stage, bit 1 plain stage
   int ring2_min_k = 4096;  // MOEINF_RING_MIN_K
@@ -210,6 +210,8 @@ struct FfnShape {
   int dtype = DT_BF16;       // activation dtype: DT_BF16, DT_F16, anything else runs as fp32
   bool f8w = false;          // the routed experts' weights are an fp8 slot (FfnStage::wdtype == DT_F8)
   bool mx4w = false;         // ... an MXFP4 slot (FfnStage::wdtype == DT_MX4)
+  bool mx4_gemm = false;     // ... of an engine with the MXFP4 grouped GEMMs switched on (moeinf_set_mxfp4_gemm; not in FfnStage, which
+                             // is a kernel argument: launch_ffn_stage sets it from an argument of its own)
   int nmat = 1;              // 2: gated stage, 1: plain
   int epi = EPI_NONE;
   int K = 0, K_sh = 0;       // reduction lengths of the routed / shared experts (K_sh = 0: no shared expert in the launch)
@@ -255,6 +257,10 @@ struct FfnForm {
   int num_cus = 0;        // big: compute units of the device (its short-pass rule)
   Ring2Form ring;         // ring2
 };
+// the LDS-staged kernel in 128-row blocks (else 64).  Plain stage: 128-row blocks need >= 2 blocks per CU to hide the DMA latency
+inline bool lds_rows128(const FfnShape& s, int active, const FfnKnobs& k) {
+  return s.nmat == 2 ? k.rgb_gated == 8 : (k.rgb_plain ? k.rgb_plain == 8 : ((s.row_groups + 7) / 8) * active >= 512 && s.K >= 4096);
+}
 // active = grid.y (upper bound of experts with rows); max_rows: see launch_ffn_stage
 inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus, const FfnKnobs& k) {
   FfnForm f;
@@ -284,8 +290,27 @@ inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus
   f.waves = nw == 8 ? 8 : 4;
   // the grouped GEMMs are built for the SiLU gate only: the gelu gate runs the row kernel at every size
   if (s.epi == EPI_GATED_GELU) return f;
-  // ... and so does an MXFP4 slot: MX4 forms of the grouped GEMMs are not built
-  if (s.mx4w) return f;
+  // ... and so does an MXFP4 slot of an engine that has not switched the MXFP4 grouped GEMMs on (moeinf_set_mxfp4_gemm; the default)
+  if (s.mx4w && !s.mx4_gemm) return f;
+  if (s.mx4w) {
+    // MXFP4 with the switch on: the fp8 rule on the two forms that are built (ffn_gemm_mx4.hip: hybrid and LDS-staged, full-line
+    // staging only; no ring2, no big kernel — DESIGN.md section 11).  The row kernel up to MOEINF_FFN_MANY_ROWS also under a forced
+    // MOEINF_FFN_NT > 1, under MOEINF_FFN_GEMM=0, and with a shared expert whose reduction is not whole 128-byte lines (K_sh % 64;
+    // K % 128 == 0 was checked above); fuse_combine never gets here.  The hybrid takes one code tile = four activation k-tiles per
+    // stage (MOEINF_GEMM_HYB_KK does not apply), both keep xl = 1 under MOEINF_GEMM_XL=0, and the gated LDS form is 64-row blocks.
+    // The 17-row and 128 / 64-row thresholds are the bf16 / fp8 ones.
+    if (max_rows <= k.many_rows || k.use_gemm == 0 || s.K_sh % 64 != 0) return f;
+    FfnForm g;
+    g.nmat = s.nmat; g.xl = 1;
+    if (k.use_gemm == 3 || max_rows <= hyb_rows_for(active, k)) {
+      g.kernel = FFN_HYB; g.waves = 4; g.rw = s.nmat == 2 ? 1 : 2; g.kk = 4;
+    } else {
+      g.kernel = FFN_LDS;
+      g.waves = (k.wide >= 0 ? k.wide != 0 : max_rows > 128) ? 8 : 4;
+      g.rgb = s.nmat == 1 && lds_rows128(s, active, k) ? 8 : 4;
+    }
+    return g;
+  }
   const int ept = (s.dtype == DT_BF16 || s.dtype == DT_F16) ? 32 : 16;  // activation elements per 64-byte k-tile
   const bool k_ok = s.K % ept == 0 && s.K_sh % ept == 0;
   int use_gemm = k.use_gemm;
@@ -334,8 +359,7 @@ inline FfnForm ffn_form(const FfnShape& s, int active, int max_rows, int num_cus
     g.kernel = FFN_LDS;
     g.waves = (k.wide >= 0 ? k.wide != 0 : max_rows > 128) ? 8 : 4;  // 8 waves: 256 tokens per pass over the weights
     // plain stage: 128-row blocks need >= 2 blocks per CU to hide the DMA latency; 64-row blocks otherwise
-    const bool rows128 = s.nmat == 2 ? k.rgb_gated == 8 : (k.rgb_plain ? k.rgb_plain == 8 : ((s.row_groups + 7) / 8) * active >= 512 && s.K >= 4096);
-    g.rgb = rows128 ? 8 : 4; g.xl = xl;
+    g.rgb = lds_rows128(s, active, k) ? 8 : 4; g.xl = xl;
   } else if (use_gemm) {  // the register GEMM (never fp8: k_ok)
     // measured: (RG,NT)=(2,4)/(4,4) beats (1,8)/(2,8) at t_e ~128 (profiles/r01_ffn_sweep_prefill_gemm.txt)
     g.kernel = FFN_GEMM; g.waves = 4; g.nt = (k.gemm_nt ? k.gemm_nt : 4) <= 4 ? 4 : 8;
@@ -659,11 +683,14 @@ inline LayerForm layer_form(const LayerShape& s, const LayerKnobs& k) {
 }
 
 // max_rows_per_expert: upper bound of rows any one expert receives (selects the kernel and its form); num_cus: of the device
-hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st);
+// mx4_gemm: FfnShape::mx4_gemm (read for MXFP4 slots only); kernel_out: if not NULL, the FFN_* id the stage took
+hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st, bool mx4_gemm = false,
+                            int* kernel_out = nullptr);
 // the grouped GEMMs, one launcher per translation unit: each maps the form ffn_form chose to its instantiation
 void launch_ffn_gemm(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);             // ffn_gemm.hip: bf16, fp32
 void launch_ffn_gemm_f16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);         // ffn_gemm_f16.hip
 void launch_ffn_gemm_f8(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);          // ffn_gemm_f8.hip: fp8 slots
+void launch_ffn_gemm_mx4(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);         // ffn_gemm_mx4.hip: MXFP4 slots (hybrid, LDS)
 void launch_ffn_gemm_ring2_bf16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);  // ffn_gemm_ring2.hip
 void launch_ffn_gemm_ring2_f16(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);   // ffn_gemm_ring2_f16.hip
 void launch_ffn_gemm_big(const FfnStage& s, dim3 grid, const FfnForm& f, hipStream_t st);         // ffn_gemm_big.hip: bf16, fp16

@@ -426,10 +426,13 @@ static void launch_ffn_rows(const FfnStage& s, dim3 grid, const FfnForm& f, hipS
 #undef LAUNCH
 }
 
-hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st) {
+hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_expert, int num_cus, hipStream_t st, bool mx4_gemm,
+                            int* kernel_out) {
   static const FfnKnobs knobs = FfnKnobs::from_env();
-  const FfnShape h = ffn_shape(s);
+  FfnShape h = ffn_shape(s);
+  h.mx4_gemm = mx4_gemm;
   const FfnForm f = ffn_form(h, max_active, max_rows_per_expert, num_cus, knobs);
+  if (kernel_out) *kernel_out = f.kernel;
   const dim3 grid(h.row_groups, max_active);
   const bool gated = f.nmat == 2;
   switch (f.kernel) {
@@ -449,6 +452,7 @@ hipError_t launch_ffn_stage(const FfnStage& s, int max_active, int max_rows_per_
       break;
     default:  // hybrid, LDS-staged, register GEMM
       if (h.f8w) launch_ffn_gemm_f8(s, grid, f, st);
+      else if (h.mx4w) launch_ffn_gemm_mx4(s, grid, f, st);
       else if (s.dtype == DT_F16) launch_ffn_gemm_f16(s, grid, f, st);
       else launch_ffn_gemm(s, grid, f, st);
   }

@@ -70,6 +70,8 @@ class MoEEngine:
             check(self.lib.moeinf_create_ex(C.byref(c), C.byref(opts), C.byref(self._h)))
         else:
             check(self.lib.moeinf_create(C.byref(c), C.byref(self._h)))
+        if cfg.mxfp4_gemm:
+            check(self.lib.moeinf_set_mxfp4_gemm(self._h, 1))
         self.dtype = _TORCH_DTYPE[cfg.dtype]
         # dtype of the expert blobs in the HOST tier (pack_expert): fp8 experts travel as e4m3fn bytes and are up-cast to bf16 in their slot
         self.host_dtype = torch.float8_e4m3fn if cfg.dtype == DTYPE_F8E4M3 else self.dtype
@@ -88,6 +90,18 @@ class MoEEngine:
         v = C.c_int32()
         check(self.lib.moeinf_slot_dtype(self._h, C.byref(v)))
         return v.value
+
+    def set_mxfp4_gemm(self, on: bool):
+        """MXFP4-slot engines: FFN stages with more than 16 rows per expert take the MXFP4 grouped GEMMs (on) or the row kernel (off,
+        the default) from the next forward on.  Raises on an engine whose slots are not MXFP4."""
+        check(self.lib.moeinf_set_mxfp4_gemm(self._h, int(bool(on))))
+
+    def last_ffn_forms(self):
+        """(stage 1, stage 2): the kernel ids (moeinf_ffn_form's out[0]: 0 rows, 1 hybrid, 2 LDS-staged, 3 ring2, 4 register GEMM, 5 big)
+        the most recent forward's two FFN stages took; -2 where a stage ran a decode launcher or did not run."""
+        v = (C.c_int32 * 2)()
+        check(self.lib.moeinf_last_ffn_forms(self._h, v))
+        return (v[0], v[1])
 
     # ---- lifecycle ---------------------------------------------------------------------------
     def close(self):

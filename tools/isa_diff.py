@@ -5,7 +5,7 @@ left the existing ones as they were (the logs profiles/*_isa_diff_vs_parent.txt)
     python tools/isa_diff.py OLD_TREE NEW_TREE [source.hip ...]      (default sources: kernels.hip layer_fused.hip)
 
 Each source of each tree is compiled with `hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only`; a kernel's body is
-its instructions from its label to s_endpgm, comments, directives and labels dropped and local label names replaced by one token
+its instructions from its label to the end of the function (.Lfunc_end), comments, directives and labels dropped and local label names replaced by one token
 (they are numbered per file).  Kernels only in NEW_TREE are listed with their instruction, scratch, conversion and MFMA counts."""
 import os
 import re
@@ -17,6 +17,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def bodies(tree, src, tmp, tag):
+    if not os.path.exists(os.path.join(tree, "moe-infinity_amd", "csrc", src)):
+        return {}  # a source one of the trees does not have: all of its kernels are new (or missing)
     out_s = os.path.join(tmp, f"{tag}_{src}.s")
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out_s,
                     os.path.join(tree, "moe-infinity_amd", "csrc", src)], check=True, capture_output=True)
@@ -26,10 +28,10 @@ def bodies(tree, src, tmp, tag):
         m = re.match(r"^(_Z\S+):", l)
         if not m:
             continue
-        end = next((j for j in range(i, len(lines)) if "s_endpgm" in lines[j]), None)
+        end = next((j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end")), None)  # (a kernel may hold several s_endpgm)
         if end is None:
             continue
-        body = [x.strip() for x in lines[i + 1:end + 1]]
+        body = [x.strip() for x in lines[i + 1:end]]
         body = [x for x in body if x and not x.startswith((";", ".")) and not re.match(r"^\S+:$", x)]
         out[m.group(1)] = [re.sub(r"\.L[A-Za-z_]*\d+_\d+|\.Ltmp\d+|\.L__\S+", "L", x) for x in body]
     return out

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""MXFP4 slots (EngineConfig.mxfp4_slots) against bf16 slots and fp8 slots, A/B/C/A/B/C, every run in a process of its own.  Legs:
+"""MXFP4 slots (EngineConfig.mxfp4_slots; mxfp4-gemm: with EngineConfig.mxfp4_gemm, the MXFP4 grouped GEMMs switched on) against bf16
+slots and fp8 slots, A/B/C/D/A/B/C/D, every run in a process of its own.  Legs:
 
     decode-mixtral     Mixtral-8x7B, 32 layers resident, batch 1: ms/token
     decode-deepseek    DeepSeek-V2-Lite, 26 layers resident, batch 1: ms/token
@@ -9,10 +10,11 @@
     prefill-mixtral    Mixtral-8x7B, 8 layers resident, 64 / 512 tokens (--tokens): ms per layer
     prefill-deepseek   DeepSeek-V2-Lite, 8 layers resident, 64 / 512 tokens (--tokens): ms per layer
 
-    python tools/mxfp4_slots_time.py [--tokens N,...] [--slots bf16,fp8,mxfp4] [--rounds N] [--trees DIR,...] [leg ...]
+    python tools/mxfp4_slots_time.py [--tokens N,...] [--slots bf16,fp8,mxfp4,mxfp4-gemm] [--rounds N] [--trees DIR,...] [leg ...]
         (default: every leg, every slot kind; one JSON line per run, then a summary.  --trees: the same runs against the library of
-        each of these checkouts in turn — e.g. the parent commit and this one; a tree without MXFP4 slots runs bf16 and fp8 only)
-    python tools/mxfp4_slots_time.py --child <leg> <bf16|fp8|mxfp4> [--steps N] [--tokens N] [--tree DIR]   (one run; used by the
+        each of these checkouts in turn — e.g. the parent commit and this one; a tree without MXFP4 slots runs bf16 and fp8 only, one
+        without the MXFP4 grouped GEMMs not mxfp4-gemm)
+    python tools/mxfp4_slots_time.py --child <leg> <bf16|fp8|mxfp4|mxfp4-gemm> [--steps N] [--tokens N] [--tree DIR]   (one run; used by the
         above and under rocprofv3)
 The expert bytes are random: fp8 blobs N(0, 0.02^2) rounded to e4m3fn, MXFP4 blobs random codes with scale bytes 115..129 (any
 codes and in-contract scales cost the same), bf16 blobs N(0, 0.02^2)."""
@@ -24,7 +26,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEGS = ["decode-mixtral", "decode-deepseek", "miss-mixtral", "tight-mixtral", "prefill-mixtral", "prefill-deepseek"]
-KINDS = ["bf16", "fp8", "mxfp4"]
+KINDS = ["bf16", "fp8", "mxfp4", "mxfp4-gemm"]
 
 
 def child(leg, kind, steps, tokens=512, tree=ROOT):
@@ -41,6 +43,8 @@ def child(leg, kind, steps, tokens=512, tree=ROOT):
         cfg = mk(dtype=Cf.DTYPE_F8E4M3, fp8_slots=True, **kw)
     elif kind == "mxfp4":
         cfg = mk(dtype=Cf.DTYPE_BF16, mxfp4_slots=True, **kw)
+    elif kind == "mxfp4-gemm":
+        cfg = mk(dtype=Cf.DTYPE_BF16, mxfp4_slots=True, mxfp4_gemm=True, **kw)
     else:
         cfg = mk(dtype=Cf.DTYPE_BF16, **kw)
     pressure = leg in ("miss-mixtral", "tight-mixtral")
@@ -61,7 +65,7 @@ def child(leg, kind, steps, tokens=512, tree=ROOT):
             view = eng.expert_host_view(l, e)
             if kind == "fp8":
                 view.copy_(torch.empty(tot, device=dev).normal_(0.0, 0.02, generator=g).to(torch.float8_e4m3fn).view(torch.uint8))
-            elif kind == "mxfp4":
+            elif kind.startswith("mxfp4"):
                 # every byte a pair of random codes; then the scale bytes of every tensor (its last 1/17) into the contract's range
                 view.copy_(torch.randint(0, 256, (tot,), device=dev, generator=g, dtype=torch.uint8))
                 for o, s in zip(off, siz):
@@ -116,6 +120,8 @@ def child(leg, kind, steps, tokens=512, tree=ROOT):
             res.update(ms_per_token=round(best * L * 1e3, 4), layers=L)
         else:
             res.update(ms_per_layer=round(best * 1e3, 4), tokens=T)
+            if hasattr(eng, "last_ffn_forms"):  # the kernels the last forward's two stages took (moeinf_ffn_form's ids)
+                res.update(ffn_forms=list(eng.last_ffn_forms()))
         res.update(slots_total=st["slots_total"], slot_bytes=st["slot_bytes"], misses_measured=st["expert_misses"])
     eng.close()
     print("RESULT " + json.dumps(res), flush=True)
@@ -130,7 +136,9 @@ def main(legs, tokens=(64, 512), trees=(ROOT,), kinds=KINDS, rounds=2):
             for tree in trees:
                 has_mx = os.path.exists(os.path.join(tree, "moe-infinity_amd", "quant.py"))
                 for kind in kinds:
-                    if kind == "mxfp4" and not has_mx:
+                    if kind.startswith("mxfp4") and not has_mx:
+                        continue
+                    if kind == "mxfp4-gemm" and not os.path.exists(os.path.join(tree, "moe-infinity_amd", "csrc", "ffn_gemm_mx4.hip")):
                         continue
                     st = max(1, steps[leg] * 512 // t) if leg.startswith("prefill") else steps[leg]
                     p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", leg, kind, "--steps", str(st), "--tokens", str(t),
@@ -153,7 +161,7 @@ def main(legs, tokens=(64, 512), trees=(ROOT,), kinds=KINDS, rounds=2):
                 key = "ms_per_token" if "ms_per_token" in rs[0] else "ms_per_layer"
                 extra = f" hit_rate {[r['hit_rate'] for r in rs]} link GB/s {[r['link_gbs'] for r in rs]}" if "hit_rate" in rs[0] else ""
                 tt = f" T={t}" if leg.startswith("prefill") else ""
-                print(f"SUMMARY {leg:18s}{tt:7s} {name:10s} {kind:5s} slots {key} {[r[key] for r in rs]}{extra}", flush=True)
+                print(f"SUMMARY {leg:18s}{tt:7s} {name:10s} {kind:10s} slots {key} {[r[key] for r in rs]}{extra}", flush=True)
         # what the misses alone would take at the link rate the bf16 run of the same leg reached
         for tree in trees:
             name = os.path.basename(os.path.abspath(tree))
